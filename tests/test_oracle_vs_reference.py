@@ -1,7 +1,7 @@
 """CPU, development container only: diff the oracle against the compiled reference (oracle/_ref/ref_dump,
-built from /root/reference by oracle/Makefile) on a matrix of gap modes x align modes x band on/off x
-score width, cell for cell.  Skipped where the reference build is absent and nothing here runs on the
-GPU box (no /root/reference there)."""
+built by oracle/Makefile) on a matrix of gap modes x align modes x band on/off x score width, cell for cell.
+Inputs are the reference's own data files as committed under tests/golden/data/.  Skipped where the reference
+build is absent."""
 import glob
 import os
 
@@ -10,7 +10,8 @@ import pytest
 import helpers as H
 from abpoa_amd import synth
 
-pytestmark = pytest.mark.skipif(not (H.have_ref() and os.path.isdir(H.REFERENCE_TREE)), reason="reference build not available")
+pytestmark = pytest.mark.skipif(not H.have_ref(), reason="reference build not available")
+DATA = os.path.join(H.GOLDEN_DIR, "data")
 
 AG, CG, LG = ["-O", "4,0", "-E", "2"], [], ["-O", "0,0", "-E", "2"]
 MODES = {"gb": [], "gu": ["-b", "-1"], "loc": ["-m", "1"], "ext": ["-m", "2"], "extz": ["-m", "2", "-z", "5"]}
@@ -31,8 +32,8 @@ def _check(tmp_path, name, fa, opts, reads, sub=None):
 @pytest.mark.parametrize("mode", list(MODES))
 def test_reference_test_data(tmp_path, gap, mode):
     g = {"ag": AG, "cg": CG, "lg": LG}[gap]
-    _check(tmp_path, "seq", os.path.join(H.REFERENCE_TREE, "test_data/seq.fa"), g + MODES[mode], "all")
-    _check(tmp_path, "het", os.path.join(H.REFERENCE_TREE, "test_data/heter.fa"), g + MODES[mode], "2,7,14")
+    _check(tmp_path, "seq", os.path.join(DATA, "seq.fa"), g + MODES[mode], "all")
+    _check(tmp_path, "het", os.path.join(DATA, "heter.fa"), g + MODES[mode], "2,7,14")
 
 
 @pytest.mark.parametrize("gap", ["ag", "cg", "lg"])
@@ -49,8 +50,8 @@ def test_linear_gaps_with_narrow_bands(tmp_path, e1, wb):
     """Linear gaps with bands of -b 2 .. 10 -f 0: rows with stretches no real score reaches (the reference clamps those lanes at `inf`, src/simd_abpoa_align.c:773-775) --
     the regime of tests/test_gpu_parity.py::test_linear_rows_plane_level_on_the_golden_graphs, which compares the fast row loops with this oracle."""
     g = ["-O", "0,0", "-E", str(e1), "-b", str(wb), "-f", "0"]
-    _check(tmp_path, "seq", os.path.join(H.REFERENCE_TREE, "test_data/seq.fa"), g, "all")
-    _check(tmp_path, "het", os.path.join(H.REFERENCE_TREE, "test_data/heter.fa"), g, "2,7,14")
+    _check(tmp_path, "seq", os.path.join(DATA, "seq.fa"), g, "all")
+    _check(tmp_path, "het", os.path.join(DATA, "heter.fa"), g, "2,7,14")
     fa = str(tmp_path / "s.fa")
     synth.write_fasta(fa, synth.make_read_set(17, 2, 8, 700, 0.12))
     _check(tmp_path, "syn", fa, g, "3,7")
@@ -66,11 +67,11 @@ def test_synthetic_10kb_int32(tmp_path):
 def test_amino_acid_blosum62(tmp_path):
     fa = str(tmp_path / "aa.fa")
     synth.write_fasta(fa, synth.make_read_set(13, 1, 8, 500, alphabet=synth.AA, rates=(0.05, 0.03, 0.03)))
-    mtx = os.path.join(H.REFERENCE_TREE, "BLOSUM62.mtx")
+    mtx = os.path.join(DATA, "BLOSUM62.mtx")
     _check(tmp_path, "loc", fa, ["-m", "1", "-c", "-t", mtx], "2,7")
     _check(tmp_path, "glob", fa, ["-c", "-t", mtx], "5")
 
 
 def test_subgraph(tmp_path):
-    _check(tmp_path, "s1", os.path.join(H.REFERENCE_TREE, "test_data/seq.fa"), AG, "3,5,8", sub=(10, 40))
-    _check(tmp_path, "s2", os.path.join(H.REFERENCE_TREE, "test_data/heter.fa"), CG, "4,9", sub=(100, 500))
+    _check(tmp_path, "s1", os.path.join(DATA, "seq.fa"), AG, "3,5,8", sub=(10, 40))
+    _check(tmp_path, "s2", os.path.join(DATA, "heter.fa"), CG, "4,9", sub=(100, 500))
