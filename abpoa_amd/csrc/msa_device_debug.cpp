@@ -218,12 +218,17 @@ void DeviceDebug::balance_report(int k, const DevBatch &b, hipEvent_t rows_begin
         fprintf(stderr,
                 "[poa-device] round %d slowest row loop: set %d ticks %lld rows %d | all-chunk body %lld | not eligible "
                         "%lld | ring-geometry %lld | > 5 chunks %lld | slow vectors straddle %lld | key window / wrap %lld\n", k, w_, (long long)o_.clk_dp,
-                        o_.n_rows_done, (long long)o_.seg[0], (long long)o_.seg[1], (long long)o_.seg[2], (long long)o_.seg[3], (long long)o_.seg[4],
+                        o_.n_rows_done, (long long)(o_.seg[0] & 0xffffffffll), (long long)o_.seg[1], (long long)o_.seg[2], (long long)o_.seg[3], (long long)o_.seg[4],
                         (long long)o_.seg[5]); }
-    if (opt_env("ABPOA_HIP_WIDE_COUNTERS")) fprintf(stderr,
+    if (opt_env("ABPOA_HIP_WIDE_COUNTERS")) {
+        // (slot 0: all-chunk body rows in bits 0-31, rows of 9-11 chunks among them in bits 32-47 (int32) / 48-62 (int16): rows_fast.h WCOUNT_BODY)
+        double body = 0, xl32 = 0, xl16 = 0; for (const AlnOut &o_ : ho) { body += (double)(o_.seg[0] & 0xffffffffll); xl32 += (double)((o_.seg[0] >> 32) & 0xffff);
+                xl16 += (double)(o_.seg[0] >> 48); }
+        fprintf(stderr,
             "[poa-device] round %d wide-loop rows per alignment (diagnostic build): all-chunk body %.0f | not eligible "
-                    "(preds > 8 / distance) %.0f | ring-geometry %.0f | > 5 chunks %.0f | slow vectors straddle %.0f | key " "window / wrap %.0f\n", k,
-                    sg[0] / n_sets, sg[1] / n_sets, sg[2] / n_sets, sg[3] / n_sets, sg[4] / n_sets, sg[5] / n_sets);
+                    "(preds > 8 / distance) %.0f | ring-geometry %.0f | > 5 chunks %.0f | slow vectors straddle %.0f | key " "window / wrap %.0f | "
+                    "9-11-chunk bodies int32 %.0f int16 %.0f\n", k,
+                    body / n_sets, sg[1] / n_sets, sg[2] / n_sets, sg[3] / n_sets, sg[4] / n_sets, sg[5] / n_sets, xl32 / n_sets, xl16 / n_sets); }
     fprintf(stderr,
             "[poa-device] round %d tail means: steps %.0f  flag steps %.0f  slow steps %.0f  windows %.1f  window ticks %.0f (setup %.0f)  walk ticks %.0f\n",
             k, st_ / n_sets, sg[2] / n_sets / 1000, sg[3] / n_sets / 1000, sg[4] / n_sets / 1000, sg[5] / n_sets, sg[0] / n_sets, sg[1] / n_sets);

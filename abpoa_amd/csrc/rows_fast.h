@@ -2,6 +2,7 @@
 #include "dp_common.h"
 #include "dir_plane.h"
 #include "rows_tight_asm.h"
+#include "wide_closed_forms.h"
 
 namespace abpoa_hip {
 
@@ -115,8 +116,11 @@ __device__ __forceinline__ void slow_f_vectors(int vbase, int end_sn, int max_pr
 #endif
 #ifdef ABPOA_HIP_WIDE_COUNTERS
 #define WCOUNT(I) { fseg[I] += 1; }
+// (single-wave wide bodies) slot 0 counts the row in its low 32 bits, a row of 9-11 chunks (the long-read form) also in bits 32-47 (int32) / 48-62 (int16)
+#define WCOUNT_BODY(NCH) { fseg[0] += 1 + ((NCH) >= 9 ? (I16 ? 1ll << 48 : 1ll << 32) : 0); }
 #else
 #define WCOUNT(I) {}
+#define WCOUNT_BODY(NCH) {}
 #endif
 #ifdef ABPOA_HIP_ABLATE
 #define ABL(BIT) (b.dbg & (BIT))
@@ -192,8 +196,8 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
     const int cf1 = oe1 - e1 + le1, cf2 = oe2 - e2 + le2;                               // F[c] = S[c] - cf
     const long long lo_ll = (long long)(I16 ? INT16_MIN : INT32_MIN) + imax(oe1, oe2) + (long long)PN * imax(e1, e2);
     const int fast_lo = (int)lo_ll;
-    const int kconst = I16 ? (int)(0x80000000u | ((unsigned)(PN - 1 - l) << 12) | (unsigned)(2047 - vvl)) : 0;
-    const int ktie = ((PN - 1 - l) << 7) | (63 - vvl);                                  // int32 wide rows: residue, then (bit 6) the end vector, then the vector order
+    const int kconst = I16 ? argmax_key16_const(PN, l, vvl) : 0;                       // (wide_closed_forms.h)
+    const int ktie = argmax_tie32(PN, l, vvl);                                          // int32 wide rows: residue, then the end vector, then the vector order
 
     // ---- LDS: extended score matrix (column m = 0) and the score ring, everything "inf"
     { GLOBAL_AS const int32_t *g_mat = vgpr_ptr(b.mat); for (int i = tid; i < m * m1; i += NT) { const int bb = i / m1, qc = i - bb * m1; s_mx[i] = qc < m ? g_mat[bb * m + qc] : 0; } }
@@ -396,7 +400,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 int cand = Hout;
                 if (end_sn == qlen_sn) cand = (is_end && col > qlen) ? inf : cand;
                 if (I16) {
-                    const unsigned key = ((unsigned)cand << 16) + (unsigned)(kconst - vb) + (is_end ? 2048u : 0u);
+                    const unsigned key = argmax_key16(cand, kconst, vb, is_end);
                     am_key = (in_band && key > am_key) ? key : am_key;
                 } else if (in_band && (!am_any || (is_end ? cand >= am_val : cand > am_val))) { am_val = cand; am_v = v; am_isend = is_end; am_any = true; }
             }
@@ -485,7 +489,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             int cand = Hout;
             if (end_sn == qlen_sn) cand = (is_end && col > qlen) ? inf : cand;
             if (I16) {
-                const unsigned key = ((unsigned)cand << 16) + (unsigned)(kconst - vb) + (is_end ? 2048u : 0u);
+                const unsigned key = argmax_key16(cand, kconst, vb, is_end);
                 am_key = (in_band && key > am_key) ? key : am_key;
             } else if (in_band && (!am_any || (is_end ? cand >= am_val : cand > am_val))) { am_val = cand; am_v = v; am_isend = is_end; am_any = true; }
         }
@@ -891,7 +895,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         const int Wr = (end_sn - beg_sn + 1) * PN;
         // this wavefront's chunks: c0 .. c0 + cnt - 1 (one wavefront: all of them; teams: nch / NW each, the first nch % NW one more)
         int c0 = 0, cnt = nch;
-        if (TEAM) { const int bs_ = nch / NW, rm_ = nch - bs_ * NW; cnt = bs_ + (wid < rm_ ? 1 : 0); c0 = wid * bs_ + imin(wid, rm_); }
+        if (TEAM) team_chunks(nch, NW, wid, c0, cnt);
         const int colb = beg_sn * PN + lane + 64 * c0;              // this lane's column in the wavefront's first chunk
         if (__builtin_expect(beg_sn != qcx_beg_sn || (TEAM && c0 != qcx_c0), 0)) {
             qcx_beg_sn = beg_sn; qcx_c0 = c0;
@@ -1016,8 +1020,8 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             const bool in_band = (!TEAM && c < NCH - 2) ? true : cg * 64 + lane < Wr, is_end = (!TEAM && c < NCH - 2) ? false : (cg * NV + vvl == relv_end);
             int cand = hsE[c]; if (end_sn == qlen_sn) cand = (is_end && colb + 64 * c > qlen) ? inf : cand;
             unsigned key;
-            if (I16) key = ((unsigned)cand << 16) + (unsigned)(kconst - vb) + (is_end ? 2048u : 0u);
-            else key = ((unsigned)imin(imax(cand, vfloor) - vfloor, 0x1FFFFF) << 11) | (unsigned)(ktie - cg * NV) | (is_end ? 64u : 0u);      // (max first: inf - floor must not wrap)
+            if (I16) key = argmax_key16(cand, kconst, vb, is_end);
+            else key = argmax_key32(cand, vfloor, ktie, cg, NV, is_end);
             amk = (in_band && key > amk) ? key : amk;
         }
         // interleaved DPP chains: F scans of every chunk + the arg-max key
@@ -1050,8 +1054,8 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         if (!TEAM) { asm("" : "+v"(seed1[0])); if (GAP == 2) asm("" : "+v"(seed2[0])); }
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            seed1[c + 1] = imax(__builtin_amdgcn_readlane(imax(s1[c], g1[c]), 63), seed1[c]) - 64 * e1;
-            if (GAP == 2) seed2[c + 1] = imax(__builtin_amdgcn_readlane(imax(s2[c], g2[c]), 63), seed2[c]) - 64 * e2; else seed2[c + 1] = INT_MIN;
+            seed1[c + 1] = carry_next(__builtin_amdgcn_readlane(imax(s1[c], g1[c]), 63), seed1[c], e1);
+            if (GAP == 2) seed2[c + 1] = carry_next(__builtin_amdgcn_readlane(imax(s2[c], g2[c]), 63), seed2[c], e2); else seed2[c + 1] = INT_MIN;
         }
         if constexpr (TEAM) {
             // exchange entry of this wavefront: {chain result out of its last chunk (two planes), arg-max key, wrap flag}
@@ -1070,8 +1074,8 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 const unsigned kj = (unsigned)__builtin_amdgcn_readlane(en.z, j);
                 anywrap |= __builtin_amdgcn_readlane(en.w, j); kall = kj > kall ? kj : kall;
                 if (j < wid) {
-                    const int bs_ = nch / NW, rm_ = nch - bs_ * NW, cj = (bs_ + (j < rm_ ? 1 : 0)) * 64;
-                    in1 = imax(a1, imax(in1, INT_MIN + cj * e1) - cj * e1); in2 = imax(a2, imax(in2, INT_MIN + cj * e2) - cj * e2);
+                    int c0j, cntj; team_chunks(nch, NW, j, c0j, cntj);
+                    in1 = carry_fold(a1, in1, cntj * 64 * e1); in2 = carry_fold(a2, in2, cntj * 64 * e2);
                 }
             }
             if (__builtin_expect(anywrap, 0)) return 0;
@@ -1079,12 +1083,12 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             if (wid > 0) {
 #pragma unroll
                 for (int c = 0; c < NCH; ++c) {
-                    seed1[c] = imax(seed1[c], imax(in1, INT_MIN + c * 64 * e1) - c * 64 * e1);
-                    if (GAP == 2) seed2[c] = imax(seed2[c], imax(in2, INT_MIN + c * 64 * e2) - c * 64 * e2);
+                    seed1[c] = carry_fold(seed1[c], in1, c * 64 * e1);
+                    if (GAP == 2) seed2[c] = carry_fold(seed2[c], in2, c * 64 * e2);
                 }
             }
         }
-        if (!I16) { const unsigned tv = kbst >> 11; if (__builtin_expect(tv == 0u || tv == 0x1FFFFFu, 0)) return 0; }
+        if (!I16) { if (__builtin_expect(argmax_declines32(kbst), 0)) return 0; }
         FSTAMP(3)
         // ---- from here on the row is committed
         T *const Hrow = io.planes + (long long)cur * PN + (long long)(lane + 64 * c0) * CWR;
@@ -1184,13 +1188,8 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         FSTAMP(4)
         // ---- row arg-max
         mi = -1;
-        if (I16) {
-            rowmax = (int)(kbst >> 16) - 32768;
-            if (rowmax > inf) { mi = (2047 - (int)(kbst & 0x7ff)) * PN + (PN - 1 - (int)((kbst >> 12) & 0xf)); if (mi > qlen) mi = -1; }
-        } else {
-            rowmax = vfloor + (int)(kbst >> 11);
-            if (rowmax > inf) { mi = (beg_sn + 63 - (int)(kbst & 63)) * PN + (PN - 1 - (int)((kbst >> 7) & 0xf)); if (mi > qlen) mi = -1; }
-        }
+        if (I16) { rowmax = argmax_value16(kbst); if (rowmax > inf) mi = argmax_index16(kbst, PN, qlen); }
+        else { rowmax = argmax_value32(kbst, vfloor); if (rowmax > inf) mi = argmax_index32(kbst, PN, beg_sn, qlen); }
         return 1;
     };
 
@@ -1358,10 +1357,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                     mi = -1;
                     if (rc == 1) {
                         if (I16) {
-                            const unsigned kb = wave_max_u32_s(am_key);
-                            const int vmax = (int)(kb >> 16) - 32768;
-                            rowmax = vmax;
-                            if (vmax > inf) { mi = (2047 - (int)(kb & 0x7ff)) * PN + (PN - 1 - (int)((kb >> 12) & 0xf)); if (mi > qlen) mi = -1; }
+                            argmax_decode16(wave_max_u32_s(am_key), PN, qlen, inf, rowmax, mi);
                         } else {
                             const int vmax = wave_max_i32_s(am_any ? am_val : INT_MIN);
                             rowmax = vmax;
@@ -1498,7 +1494,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                         else ok2 = ilp_chunks(std::integral_constant<int, 11>{}, nch_, row, ti);
                     }
                     else ok2 = 0;
-                    if (ok2 == 1) { WCOUNT(0); commit_row(ti, true); FSTAMP(5) ++row; continue; }
+                    if (ok2 == 1) { WCOUNT_BODY(nch_); commit_row(ti, true); FSTAMP(5) ++row; continue; }
                     WCOUNT(5);
                 }
             } else if (WIDEB) WCOUNT(1);
@@ -1516,10 +1512,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 // ---- row arg-max (tie-break: lowest lane residue, then the end_sn vector, then the lowest vector), reference :1043-1057
                 mi = -1;
                 if (I16) {
-                    const unsigned kb = wave_max_u32_s(am_key);
-                    const int vmax = (int)(kb >> 16) - 32768;
-                    rowmax = vmax;
-                    if (vmax > inf) { mi = (2047 - (int)(kb & 0x7ff)) * PN + (PN - 1 - (int)((kb >> 12) & 0xf)); if (mi > qlen) mi = -1; }
+                    argmax_decode16(wave_max_u32_s(am_key), PN, qlen, inf, rowmax, mi);
                 } else {
                     const int vmax = wave_max_i32_s(am_any ? am_val : INT_MIN);
                     rowmax = vmax;

@@ -54,6 +54,13 @@ def cases(tmp):
     s20k = os.path.join(tmp, "s20k.fa")                 # reads above 16 K bases: query beyond the old LDS limit of the fast row loops, band of ~440 columns
     synth.write_fasta(s20k, synth.make_read_set(3, 0, 4, 20000, 0.05))
     out.append(("s20k_ag_i32", s20k, AG, "3", 0, None))
+    # rows of 9-11 chunks (577-704 columns: the long-read form of the wide row loop, dp_xl_rows.hip) from a band of -b 300 on 3 kb reads; match 12 takes
+    # the scores into int32 (12 x 3 000 > 32 767), the default match keeps an int16 twin
+    s3k = os.path.join(tmp, "s3k.fa")
+    synth.write_fasta(s3k, synth.make_read_set(4, 0, 6, 3000, 0.08))
+    out.append(("s3k_ag_i32_b300", s3k, AG + ["-b", "300", "-M", "12"], "4", 0, None))
+    out.append(("s3k_cg_i32_b300", s3k, CG + ["-b", "300", "-M", "12"], "4", 0, None))
+    out.append(("s3k_ag_b300", s3k, AG + ["-b", "300"], "4", 0, None))
     out.append(("aa_blosum_loc", aa, ["-m", "1", "-c", "-t", os.path.join(REF, "BLOSUM62.mtx"), "-r", "1"], "3,7", 0, None))
     out.append(("aa_blosum_gb", aa, ["-c", "-t", os.path.join(REF, "BLOSUM62.mtx")], "7", 0, None))
     # local alignment of reads with ragged ends (every read but the first a random substring of its noisy full-length version): read 9's best path enters the

@@ -5,6 +5,7 @@ the loaded register is defined at the load.  If it spills such a register betwee
 arrived yet -- the all-rounds kernel (128 vector registers per wavefront) did exactly that in its int32 / convex backtrack until its
 staging batches were made smaller, and faulted on the GPU.  tools/check_async_spans.py finds the pattern in the assembly."""
 import os
+import re
 import subprocess
 import sys
 
@@ -14,16 +15,49 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "abpoa_amd", "csrc")
 
 
-@pytest.mark.parametrize("unit", ["poa_rounds", "dp_fast_tail"])
-def test_no_spill_between_async_load_and_wait(unit, tmp_path):
+_ASM = {}
+
+
+def _device_asm(unit, tmp_path_factory):
+    """(assembly path, resource-usage remarks) of one kernel translation unit, compiled once per session."""
+    if unit not in _ASM:
+        asm = tmp_path_factory.mktemp("asm") / (unit + ".s")
+        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-variable", "-Wno-unused-function", "-Wno-inline-asm", "--offload-arch=gfx950",
+               "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", "-o", str(asm), os.path.join(CSRC, unit + ".hip"),
+               "-Rpass-analysis=kernel-resource-usage"]
+        if unit == "poa_rounds":
+            cmd.append("-falign-loops=32")                                 # (as the Makefile builds it)
+        r = subprocess.run(cmd, check=True, cwd=CSRC, timeout=900, capture_output=True, text=True)
+        _ASM[unit] = (str(asm), r.stderr)
+    return _ASM[unit]
+
+
+@pytest.mark.parametrize("unit", ["poa_rounds", "dp_fast_tail", "dp_wide_rows", "dp_xl_rows", "dp_team_rows"])
+def test_no_spill_between_async_load_and_wait(unit, tmp_path_factory):
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")
-    asm = tmp_path / (unit + ".s")
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-variable", "-Wno-unused-function", "-Wno-inline-asm", "--offload-arch=gfx950",
-           "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", "-o", str(asm), os.path.join(CSRC, unit + ".hip")]
-    subprocess.run(cmd, check=True, cwd=CSRC, timeout=900, capture_output=True)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_async_spans.py"), str(asm)], capture_output=True, text=True)
+    asm, _ = _device_asm(unit, tmp_path_factory)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_async_spans.py"), asm], capture_output=True, text=True)
     assert p.returncode == 0, p.stdout[-3000:]
+
+
+def test_assembly_row_loop_kernels_own_its_registers(tmp_path_factory):
+    """The hand-placed assembly row loop (rows_tight_asm.h) lists v92-v127 as clobbered: the all-rounds kernels that hold it (affine, convex) must be
+    allocated all 128 VGPRs, or the compiler would be free to keep live values there."""
+    if not os.path.exists("/opt/rocm/bin/hipcc"):
+        pytest.skip("no hipcc")
+    _, remarks = _device_asm("poa_rounds", tmp_path_factory)
+    vgprs, cur = {}, None
+    for ln in remarks.splitlines():
+        m = re.search(r"Function Name: (\S+)", ln)
+        if m:
+            cur = m.group(1)
+        m = re.search(r"remark:\s+VGPRs: (\d+)", ln)
+        if m and cur:
+            vgprs[cur] = int(m.group(1))
+    for gap in (1, 2):
+        name = "_ZN9abpoa_hip17poa_rounds_kernelILi%dEEEvii" % gap
+        assert vgprs.get(name, 0) >= 128, (name, vgprs)
 
 
 HOST_RULES = r"""

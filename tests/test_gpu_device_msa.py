@@ -260,6 +260,14 @@ CIGAR_JOBS = {
     # wide bands (10 kb reads: the all-chunks row loop, column-slice backtrack windows), 5 % and 15 % errors
     "wide_affine_5": (dict(gap_open1=4, gap_open2=0, gap_ext1=2), [(8, 10000 + 17 * i, 0.05) for i in range(4)]),
     "wide_convex_15": (dict(), [(8, 10000 - 23 * i, 0.15) for i in range(4)]),
+    # long reads (the long-read form of the wide row loop, dp_xl_rows.hip: rows of 9-11 chunks): 26 kb reads score in int32 (2 x 26 000 > 32 767)
+    # (test_long_read_rows_take_the_all_chunk_bodies pins it).  The int16 8 kb and the int32 3 kb jobs under a wide band (-b 200 / 300) are cigar checks of
+    # their own: the device-resident driver does not give them the wide row loop (its row counters show no all-chunk body rows there)
+    "long_reads_i32": (dict(), [(4, 26000 + 37 * i, 0.05) for i in range(4)]),
+    "long_reads_i32_affine": (dict(gap_open1=4, gap_open2=0, gap_ext1=2), [(4, 26000 + 37 * i, 0.05) for i in range(4)]),
+    "long_reads_i16": (dict(extra_b=200), [(4, 8000 + 37 * i, 0.05) for i in range(4)]),
+    "xl_i32_b300": (dict(match=12, extra_b=300), [(6, 3000 + 41 * i, 0.08) for i in range(4)]),
+    "xl_i32_b300_affine": (dict(gap_open1=4, gap_open2=0, gap_ext1=2, match=12, extra_b=300), [(6, 3000 + 41 * i, 0.08) for i in range(4)]),
     # the general kernel's own jobs on the device-resident driver (tests/test_gpu_device_general.py): linear gaps, extension mode, no band
     "linear_banded": (dict(gap_open1=0, gap_open2=0, gap_ext1=2), [(9, 400 + 90 * i, 0.06) for i in range(6)]),
     "extend_convex": (dict(aln_mode=2), [(9, 500 + 70 * i, 0.10) for i in range(6)]),
@@ -268,10 +276,15 @@ CIGAR_JOBS = {
 
 
 @pytest.mark.parametrize("job,env", [("narrow_affine", {}), ("narrow_affine", {"ABPOA_HIP_LOCKSTEP": "1"}), ("narrow_convex_noisy", {}), ("narrow_convex_noisy", {"ABPOA_HIP_LOCKSTEP": "1"}),
-                                     ("narrow_1500", {}), ("narrow_1500", {"ABPOA_HIP_DBG": "1024"}), ("narrow_1500", {"ABPOA_HIP_DEVICE_GENERAL": "1"}),
+                                     ("narrow_affine", {"ABPOA_HIP_DBG": "2048"}),
+                                     ("narrow_1500", {}), ("narrow_1500", {"ABPOA_HIP_DBG": "1024"}), ("narrow_1500", {"ABPOA_HIP_DBG": "2048"}), ("narrow_1500", {"ABPOA_HIP_DEVICE_GENERAL": "1"}),
                                      ("linear_banded", {}), ("linear_banded", {"ABPOA_HIP_LOCKSTEP": "1"}), ("linear_banded", {"ABPOA_HIP_DEVICE_GENERAL": "1"}), ("extend_convex", {}), ("affine_unbanded", {}),
                                      ("wide_affine_5", {"ABPOA_HIP_DIR_WIDE": "0"}), ("wide_affine_5", {"ABPOA_HIP_DIR_WIDE": "1"}), ("wide_affine_5", {"ABPOA_HIP_DIR_WIDE": "1", "ABPOA_HIP_RING_ROWS": "4"}),
-                                     ("wide_convex_15", {"ABPOA_HIP_DIR_WIDE": "0"}), ("wide_convex_15", {"ABPOA_HIP_DIR_WIDE": "1"}), ("wide_convex_15", {"ABPOA_HIP_DIR_WIDE": "1", "ABPOA_HIP_RING_ROWS": "4"})],
+                                     ("wide_convex_15", {"ABPOA_HIP_DIR_WIDE": "0"}), ("wide_convex_15", {"ABPOA_HIP_DIR_WIDE": "1"}), ("wide_convex_15", {"ABPOA_HIP_DIR_WIDE": "1", "ABPOA_HIP_RING_ROWS": "4"}),
+                                     ("long_reads_i32", {}), ("long_reads_i32", {"ABPOA_HIP_DIR_WIDE": "0"}), ("long_reads_i32", {"ABPOA_HIP_DIR_WIDE": "1"}),
+                                     ("long_reads_i32_affine", {"ABPOA_HIP_DIR_WIDE": "0"}), ("long_reads_i32_affine", {"ABPOA_HIP_DIR_WIDE": "1"}),
+                                     ("long_reads_i16", {}), ("xl_i32_b300", {}), ("xl_i32_b300_affine", {"ABPOA_HIP_DIR_WIDE": "0"}),
+                                     ("xl_i32_b300_affine", {"ABPOA_HIP_DIR_WIDE": "1"})],
                          ids=lambda v: v if isinstance(v, str) else ("default" if not v else "_".join(f"{k[10:].lower()}{x}" for k, x in v.items())))
 def test_device_driver_cigars_equal_the_oracle_backed_run(engine, job, env):
     """Direct cigar comparison (not only consensus / coverage).  With ABPOA_HIP_CIGAR_DIGEST=1 the fuse phase of the device-resident driver folds the graph
@@ -312,3 +325,67 @@ def test_device_driver_cigars_equal_the_oracle_backed_run(engine, job, env):
     # (banded linear jobs: the fast row loops and the all-rounds kernel since round 5 -- H records, lane-parallel linear backtrack steps)
     narrow_all_rounds = (job.startswith("narrow") or job == "linear_banded") and "ABPOA_HIP_LOCKSTEP" not in env and "ABPOA_HIP_DEVICE_GENERAL" not in env
     assert ("ROUNDS_LAUNCHES 0" not in r.stdout) == narrow_all_rounds, r.stdout
+
+
+def test_assembly_row_loop_equals_the_compiler_loop():
+    """The headline workload's narrow rows run the hand-placed assembly loop (rows_tight_asm.h); ABPOA_HIP_DBG=2048 runs the compiler's loop of the same
+    body instead (rows_fast.h asm_tight_on).  cfg2 sets with and without it: identical consensus, and both hash to the committed reference digests
+    (tests/golden/bench_digests/cfg2.json)."""
+    import json
+    import subprocess
+    import sys
+    idx = [0, 1, 2, 3, 999]
+    code = ("import sys, json; sys.path.insert(0, %r)\n"
+            "from abpoa_amd import api, ffi, synth, workloads as W\n"
+            "ffi.check(ffi.lib().abpoa_hip_init(0))\n"
+            "w = W.WORKLOADS['cfg2']; idx = %r\n"
+            "sets = [synth.make_read_set(1, i, **synth.CONFIGS[w['cfg']]) for i in idx]\n"
+            "res = api.msa_batch(sets, api.Params(**w['params']), out_cons=True, out_msa=False)\n"
+            "assert all(r.status == 0 for r in res)\n"
+            "print('SHA', json.dumps([W.output_sha(api.format_output(r, ['r%%d' %% j for j in range(len(sets[0]))], True, False)) for r in res]))\n" % (ROOT, idx))
+    outs = []
+    for env in ({}, {"ABPOA_HIP_DBG": "2048"}):
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=dict(os.environ, **env), timeout=600)
+        assert r.returncode == 0, (env, r.stdout[-1500:], r.stderr[-3000:])
+        outs.append(json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("SHA ")][-1][4:]))
+    from abpoa_amd import workloads as W
+    ref = W.load_digests("cfg2")
+    assert outs[0] == outs[1] == [ref[i] for i in idx]
+
+
+# the long-read jobs above and the score width their rows of 9-11 chunks run in
+LONG_ROW_JOBS = {"long_reads_i32": 32, "long_reads_i32_affine": 32}
+
+
+@pytest.mark.slow
+def test_long_read_rows_take_the_all_chunk_bodies(tmp_path):
+    """The long-read jobs of CIGAR_JOBS do test what they are there for: the diagnostic build's row counters (Makefile `counters`,
+    -DABPOA_HIP_WIDE_COUNTERS) report rows completed by the 9-11-chunk bodies of the long-read form in the job's score width (and none in the other),
+    and no row declined by the arg-max key window or the wrap guard.  (With a 6-bit vector order in the int32 key, vector 64 of every such row wrapped
+    into the key's value bits and declined nearly every row.)"""
+    import re
+    import subprocess
+    import sys
+    csrc = os.path.join(ROOT, "abpoa_amd", "csrc")
+    lib = str(tmp_path / "libabpoa_hip_wc.so")
+    b = subprocess.run(["make", "-C", csrc, "counters", "WC_OBJDIR=" + str(tmp_path / "obj"), "WC_OUT=" + lib], capture_output=True, text=True, timeout=1500)
+    assert b.returncode == 0, b.stderr[-3000:]
+    env = dict(os.environ, ABPOA_HIP_LIB=lib, ABPOA_HIP_WIDE_COUNTERS="1", ABPOA_HIP_DBG="128", ABPOA_HIP_DEVSYNC="1", ABPOA_HIP_IMBAL="1")
+    for job, bits in LONG_ROW_JOBS.items():
+        kw, shapes = CIGAR_JOBS[job]
+        code = ("import sys; sys.path.insert(0, %r)\n"
+                "from abpoa_amd import api, ffi, synth\n"
+                "ffi.check(ffi.lib().abpoa_hip_init(0))\n"
+                "sets = [synth.make_read_set(23, i, n, ln, err) for i, (n, ln, err) in enumerate(%r)]\n"
+                "res = api.msa_batch(sets, api.Params(**%r), n_threads=4)\n"
+                "assert all(r.status == 0 for r in res) and api.msa_timing()['n_host_sets'] == 0\n"
+                "print('DONE')\n" % (ROOT, shapes, kw))
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0 and "DONE" in r.stdout, (job, r.stdout[-1500:], r.stderr[-3000:])
+        rows = re.findall(r"wide-loop rows per alignment \(diagnostic build\): all-chunk body ([\d.]+) .*key window / wrap ([\d.]+) \| "
+                          r"9-11-chunk bodies int32 ([\d.]+) int16 ([\d.]+)", r.stderr)
+        assert len(rows) == max(n for n, _, _ in shapes) - 1, (job, r.stderr[-3000:])          # one line per alignment round
+        declined = sum(float(x[1]) for x in rows)
+        long32, long16 = sum(float(x[2]) for x in rows), sum(float(x[3]) for x in rows)
+        assert declined == 0, (job, rows)
+        assert (long32 > 0 and long16 == 0) if bits == 32 else (long16 > 0 and long32 == 0), (job, rows)
