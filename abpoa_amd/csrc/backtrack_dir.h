@@ -40,17 +40,49 @@ typedef DirBtT<DBTR> DirBt;
 // match runs in a table in LDS (row -> column | index of the cigar word), and when the main walk steps on a cell the helper has been on it stops:
 // the rest of its cigar is the helper's, from that word on.  No merge (the helper started on a branch the real path never touches): the main
 // wavefront simply walks to the end itself.  spec_ctl: eight ints of static LDS (hand-over flags and the helper's results); gen: the round, != 0.
-constexpr int SPEC_PM_ROWS = 256;      // rows below a helper's start row that its table covers
-constexpr int SPEC_WK = 4;             // wavefronts on a walk: the main one and three helpers, which start at 3/4, 1/2 and 1/4 of the graph
+// (SPEC_PM_ROWS = 256: rows below a helper's start row that its table covers; SPEC_WK = 4: wavefronts on a walk, the main one and three helpers -- engine.h)
 // (what both wavefronts can tell before the row loop has finished: graphs of at least 768 rows; cigar indices and columns must fit the table's 16-bit fields)
 __device__ __forceinline__ bool dir_walk_pair(const DevBatch &b, const AlnDesc &d) { return d.n_rows >= 768 && d.cigar_cap < 65536 && d.qlen < 65536 && b.ret_cigar; }
+// EARLY START (LdsPlan.te_on; the all-rounds kernel's default wherever the LDS split fits): everything a helper reads -- direction words, band geometry and
+// row_max_i of rows at or below its start row -- is final as soon as the row loop has passed that row, so the helpers walk WHILE the row loop still runs on the
+// fourth wavefront, and what is left behind the last row is the main walk from the sink down to the first helper's path, and the splice.
+//   * Progress word (an int of the workgroup's static LDS, 0 at the start of a round): after every flush of a 64-row tile's geometry the row loop writes
+//     "rows below R are complete" (rows_fast.h), and behind its last row R | SPEC_PROG_FINAL -- or SPEC_PROG_ABANDON when it ended with a status.  A helper
+//     sleeps until R is above its start row; FINAL below it (a row loop that stopped early), ABANDON, or SPEC_WAIT_POLLS polls without either and it reports
+//     "no helper" (status -1), after which the main wavefront walks alone as it always could: no wait in here is unbounded.
+//   * Visibility.  Writer and readers are wavefronts of ONE workgroup, hence of one CU, and share its vector L1: that cache is write-through and every store
+//     of the CU passes through it, so a line a helper read in the previous round (same arena addresses) cannot outlive the row loop's store to it.  What the
+//     hand-over needs is ORDER only: the row loop waits for the acknowledgement of its stores (s_waitcnt vmcnt(0)) before it writes the progress word, and
+//     every helper load of that data -- geometry, row_max_i, the LDS-DMA of the windows -- is a vector load issued after the poll that saw the word.  This
+//     is what the late start relied on as well (vmcnt(0) in WG_SYNC, then the "tables are clear" flag in LDS); only the flag has changed.
+//   * The tables are cleared by the working wavefront before its first row, so everything that writes or reads them is ordered behind that by the progress
+//     word (helpers) or by program order (the main walk).
+//   * LDS: the helpers' images, windows and tables lie behind the row loop's score ring; the main walk's region aliases the ring (it walks after the rows).
+//   * Start rows, a function of n_rows alone: 14/16, 11/16 and 6/16 of the graph (late start: 3/4, 1/2, 1/4).  The main walk -- all that is left on the
+//     critical path -- keeps an eighth of the rows, enough for its path to run into the first helper's within that helper's 256 table rows.  A step of a
+//     walk costs about a third of a row of the row loop, and the progress word lags the rows by up to a tile: helper 1 has the time of (n/8 - 64) rows for
+//     3 n/16 rows of walk, helper 2 that of (5 n/16 - 64) rows for 5 n/16, helper 3 all it needs.  A helper that is late only makes the main walk wait
+//     for it as it did before.  Tables (the 256 rows below a start row) and their 16-bit fields are as before: dir_walk_pair bounds cigar indices and columns.
+constexpr int SPEC_PROG_FINAL = 1 << 30, SPEC_PROG_ABANDON = -1;
+constexpr int SPEC_WAIT_POLLS = 1 << 16;      // x two s_sleep 127 (about 16 k cycles): far beyond the longest row loop of an alignment this kernel takes
+__device__ __forceinline__ bool dir_walk_early(const DevBatch &b, const AlnDesc &d) { return b.lds.te_on != 0 && dir_walk_pair(b, d); }
+__device__ __forceinline__ int spec_start_row(const bool early, const int gn, const int r) {
+    return early ? (int)(((long long)gn * (r == 1 ? 14 : (r == 2 ? 11 : 6))) >> 4) : (int)(((long long)gn * (SPEC_WK - r)) / SPEC_WK);
+}
+// byte offsets (from LdsPlan.phase_off) of walk r's region and of the tables, and the region's size
+__device__ __forceinline__ int spec_region(const DevBatch &b, const bool early, const int r, int &bytes, int &pm_off) {
+    if (early) { bytes = r == 0 ? b.lds.te_main : b.lds.te_w; pm_off = b.lds.te_main + (SPEC_WK - 1) * b.lds.te_w; return r == 0 ? 0 : b.lds.te_main + (r - 1) * b.lds.te_w; }
+    const int total_lds = b.lds.bt_off + b.lds.bt_bytes_tail;
+    bytes = ((total_lds - (SPEC_WK - 1) * SPEC_PM_ROWS * 4) / SPEC_WK) & ~15; pm_off = SPEC_WK * bytes;      // each walk's share of the backtrack region; the tables sit behind them
+    return r * bytes;
+}
 // More than one helper: helper r notes its cells in table r and looks the cells of its own runs up in the table of the next wavefront down whose rows it has
 // reached, exactly as the main wavefront does; the cigar is then a chain -- main, then from the word where main met helper a on, then from where a met b ...
 // spec_ctl: 8 ints per wavefront (ints 0..7: [0] = "tables are clear", set by the main wavefront; helper r: [8r] done, status, words, j, start_i, start_j,
 // steps, met << 16 | index -- -1: walked to the end).  DBR: rows a window holds at most (64 per wavefront when four share the backtrack's LDS).
 template <typename T, int GAP, int DBR = DBTR>
 __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const AlnDesc &d, AlnOut *out_rec, const TailState &ts, const int role = -1,
-                                                     int *spec_ctl = nullptr, const int gen = 0) {
+                                                     int *spec_ctl = nullptr, const int gen = 0, const int *spec_prog = nullptr) {
     constexpr int PN = Width<T>::PN, CW = FastFmt<T, GAP>::CW, DB = DirFmt<T, GAP>::DB, S = (int)sizeof(T);
     constexpr int ALIGN = 16 / DB;                    // columns per 16-byte piece of a row of words
     constexpr int DBL = DB == 2 ? 1 : 2;
@@ -78,18 +110,30 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
     // ---- two wavefronts on the walk?
     typedef __attribute__((address_space(3))) volatile int lds_vint_t;
     const bool spec_static = role >= 0 && dir_walk_pair(b, d), spec = spec_static && status == 0;
-    // helper r starts at row gn (4 - r) / 4; its table covers the 256 rows below
-    auto start_row = [&](int r_) __attribute__((always_inline)) { return (int)(((long long)gn * (SPEC_WK - r_)) / SPEC_WK); };
+    const bool early = spec_static && dir_walk_early(b, d);      // (the helpers walk under the row loop: header comment)
+    // helper r's start row; its table covers the 256 rows below
+    auto start_row = [&](int r_) __attribute__((always_inline)) { return spec_start_row(early, gn, r_); };
     const int R_g = spec && role >= 1 ? start_row(role) : 0, R_lo = R_g - SPEC_PM_ROWS + 1;
-    const int total_lds = b.lds.bt_off + b.lds.bt_bytes_tail;
-    const int half_lds = spec_static ? ((total_lds - (SPEC_WK - 1) * SPEC_PM_ROWS * 4) / SPEC_WK) & ~15 : total_lds;      // each walk's share of the backtrack region; the tables sit behind them
-    int *pm_all = (int *)(lds_raw + b.lds.phase_off + SPEC_WK * half_lds);      // table of helper r: pm_all + (r - 1) * SPEC_PM_ROWS
+    int half_lds = b.lds.bt_off + b.lds.bt_bytes_tail, pm_off = 0, reg_off = 0;      // this walk's share of the backtrack region
+    if (spec_static) reg_off = spec_region(b, early, role, half_lds, pm_off);
+    int *pm_all = (int *)(lds_raw + b.lds.phase_off + pm_off);      // table of helper r: pm_all + (r - 1) * SPEC_PM_ROWS
     int *pm = pm_all + (role >= 1 ? role - 1 : 0) * SPEC_PM_ROWS;
     lds_vint_t *ctl = (lds_vint_t *)spec_ctl, *my = ctl + 8 * (role > 0 ? role : 0);
     auto helper_out = [&](int st_) __attribute__((always_inline)) { if (lane == 0) my[1] = st_; asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); if (lane == 0) my[0] = gen; };
     if (role >= 1) {
         // helper (it has waited for the main wavefront's "tables are clear", which also says the row loop's stores have landed: fast_tail.h): the start cell
         if (!spec) { if (spec_static) helper_out(-1); return; }
+        if (early) {      // ... not before the row loop has passed the start row
+            bool go = false;
+            for (int polls = 0; polls < SPEC_WAIT_POLLS; ++polls) {
+                const int v = ((lds_vint_t *)spec_prog)[0];
+                if (v < 0) break;                                                  // the row loop ended with a status
+                if ((v & (SPEC_PROG_FINAL - 1)) > R_g) { go = true; break; }       // rows up to R_g are complete
+                if (v & SPEC_PROG_FINAL) break;                                    // it ended below the start row
+                __builtin_amdgcn_s_sleep(127); __builtin_amdgcn_s_sleep(127);
+            }
+            if (!go) { helper_out(-1); return; }
+        }
         const int c_g = __builtin_amdgcn_readfirstlane(gld_i32(vgpr_ptr(b.row_max_i + d.row0) + R_g));
         if (c_g < 1 || c_g > qlen) { helper_out(-1); return; }      // (no usable start: status -1 = "no helper")
         best_i = R_g; best_j = c_g;
@@ -122,7 +166,7 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
     int n_cigar = 0, node_s = 0, node_e = 0, query_s = 0, query_e = 0, n_aln = 0, n_match = 0;
     long long win_ticks = 0, walk_ticks = 0; int n_windows = 0, n_general = 0;
     long long dbg_why = 0, dbg_a = 0, dbg_b = 0;      // (dead end of the walk: where and on what, for AlnOut.seg under ABPOA_HIP_DBG bit 8)
-    if (spec_static && role == 0) {      // clear the tables, then let the helpers go (whatever the row loop's status: they wait for this)
+    if (spec_static && role == 0 && !early) {      // late start: clear the tables, then let the helpers go (whatever the row loop's status: they wait for this)
         for (int t = lane; t < (SPEC_WK - 1) * SPEC_PM_ROWS; t += 64) pm_all[t] = 0;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         if (lane == 0) ctl[0] = gen;
@@ -130,7 +174,7 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
     if (status == 0 && b.ret_cigar && d.cigar_cap < gn + qlen + 2) status = ABPOA_HIP_EBACKTRACK;      // (a walk emits at most one word per row or column it leaves: no per-step capacity test)
     if (role >= 1 && status != 0) { helper_out(-1); return; }
     if (status == 0 && b.ret_cigar) {
-        const int lds0 = b.lds.phase_off + (role >= 1 ? role * half_lds : 0);
+        const int lds0 = b.lds.phase_off + reg_off;
         DirBt &B = *(DirBt *)(lds_raw + lds0);
         unsigned char *win = lds_raw + lds0 + (int)sizeof(DirBt);
         const int win_bytes = half_lds - (int)sizeof(DirBt);

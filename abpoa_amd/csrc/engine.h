@@ -76,7 +76,13 @@ struct LdsPlan {
     int32_t mx_off;               // int32 [m*(m+1)]: score matrix with an extra all-zero query column (code m = "no query base")
     int32_t total;                // dynamic LDS bytes to request (general kernel: union of every phase)
     int32_t total_rows, total_tail;   // the two fast-path kernels request only what their phase needs (4+ workgroups per CU must fit)
+    // --- all-rounds kernel, helpers of the backtrack walking while the row loop still runs (backtrack_dir.h; te_on = 0: they start after it, all four walks
+    //     share the backtrack region): region of the main walk and of the score ring [0, te_main), three helper regions of te_w bytes each, then the helpers' tables
+    int32_t te_on, te_main, te_w;
 };
+constexpr int SPEC_PM_ROWS = 256;      // backtrack_dir.h: rows below a helper's start row that its table covers
+constexpr int SPEC_WK = 4;             // backtrack_dir.h: wavefronts on a walk, the main one and three helpers
+constexpr int SPEC_EARLY_MIN = 6 * 1024;      // smallest helper region with which the helpers start early (msa_device.cpp, the rounds block)
 
 // Everything one launch needs; passed by value as the kernel argument.
 struct DevBatch {

@@ -21,6 +21,7 @@ const Row kTable[] = {
     {"ABPOA_HIP_NO_DEVICE_GENERAL", "T  1: general-kernel jobs on the host driver"},
     {"ABPOA_HIP_DEVICE_GENERAL", "T  1: the general kernel for every device-resident job"},
     {"ABPOA_HIP_LOCKSTEP", "T  1: one launch per phase and round also where the all-rounds kernel would run"},
+    {"ABPOA_HIP_LATE_TAIL", "T  1: the helpers of the all-rounds kernel's backtrack start after the row loop, not under it"},
     {"ABPOA_HIP_NODIR", "T  1: score-record arenas instead of direction words"},
     {"ABPOA_HIP_DIR_WIDE", "T  1 / 0: direction words for wide-band alignments always / never (default: by residency and memory)"},
     {"ABPOA_HIP_NOFAST", "T  1: no fast row loops (general kernel)"},

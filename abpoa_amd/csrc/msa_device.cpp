@@ -326,9 +326,14 @@ static int run_msa_device_body(const abpoa_hip_scoring_t *sc_in, int n_sets, con
             //  CWR)
             const int64_t recb = wide_s ? ((bits == 16 && CW == 4) ? 4 : 8) : CW * (bits / 8);
             // (local row loop, rows_local.h: every row the whole query wide, cell records, 64 records of slack behind the last row)
-            const int64_t bytes = local ? (int64_t)up((size_t)((width * cap + 64) * CW * (bits / 8) + 64 * 8 * 4))
+            int64_t bytes = local ? (int64_t)up((size_t)((width * cap + 64) * CW * (bits / 8) + 64 * 8 * 4))
                                 : dir_s ? (int64_t)up((size_t)(width * (DB + recb) + (est * DB + est * recb / rec_div + 32) * (cap - 1) + 64 * 8 * 4))
                                       : (int64_t)up((size_t)((width + est * (cap - 1)) * CW * (bits / 8) + 64 * 8 * 4));
+            // (tests, as in the flat engine: under-sized arenas in the 3x pass -- room for the first rows, then the row loops of its sets end with the overflow
+            //  status in mid-graph and a later pass redoes them)
+            { const char *pct_ = opt_env("ABPOA_HIP_ARENA_PCT");
+              if (pct_ && !local && node_factor <= 3.0 && atoi(pct_) > 0 && atoi(pct_) < 100)
+                  bytes = std::max<int64_t>((int64_t)up((size_t)(2 * width * (DB + recb) + 64 * 8 * 4)), (int64_t)up((size_t)(bytes * atoi(pct_) / 100))); }
             S.plane_off = plane_tot; S.plane_cap = bytes - 64 * 8 * 4; plane_tot += bytes;
         }
     };
@@ -567,6 +572,20 @@ static int run_msa_device_body(const abpoa_hip_scoring_t *sc_in, int n_sets, con
                 rounds_lds = dyn_of(b_r); nb = poa_rounds_residency(sc->gap_mode, rounds_lds, &st_lds);
             }
         }
+        // Helpers of the backtrack that walk while the row loop still runs (backtrack_dir.h, EARLY START) need LDS of their own: the score ring -- or the main
+        // walk's region, whichever is larger; the main walk comes after the rows and may alias the ring -- then three helper regions, then the tables, all inside
+        // the dynamic LDS the launch has anyway, so the residency above is untouched.  Equal quarters when a quarter holds the ring (the late start's very
+        // split); else the ring's bytes in front and a third of the rest per helper.  A helper region under SPEC_EARLY_MIN (6 KB: a 1.5 KB image and 18 whole
+        // rows of a 1 kb int16 band, just above the 16 below which the windows fall back to column slices) keeps the late start, and so does
+        // ABPOA_HIP_LATE_TAIL=1 (for comparison in one process).
+        b_r.lds.te_on = 0;
+        if (b_r.dir_mode && sc->gap_mode != ABPOA_HIP_LINEAR_GAP && !(opt_env("ABPOA_HIP_LATE_TAIL") && atoi(opt_env("ABPOA_HIP_LATE_TAIL")))) {
+            const int avail = (int)rounds_lds - b_r.lds.phase_off, tables = (SPEC_WK - 1) * SPEC_PM_ROWS * 4;
+            const int ring = (b_r.lds.total_rows - b_r.lds.phase_off + 15) & ~15;
+            int w_ = ((avail - tables) / SPEC_WK) & ~15, m_ = w_;
+            if (w_ < ring) { m_ = ring; w_ = ((avail - tables - m_) / (SPEC_WK - 1)) & ~15; }
+            if (w_ >= SPEC_EARLY_MIN) { b_r.lds.te_on = 1; b_r.lds.te_main = m_; b_r.lds.te_w = w_; }
+        }
         // The kernel pays when every read-set of the job is resident at once (one workgroup each; 4 per CU): a larger job runs faster with one
         // launch per phase and round, whose single-wavefront row-loop kernel then has several alignments per SIMD to hide latency behind
         // (measured, 1 kb reads: 1000 sets 13.0 k vs 10.4 k read-sets/s; 2000 sets 12.9 k vs 13.6 k; 4000 sets 13.2 k vs 17.4 k)
@@ -574,8 +593,8 @@ static int run_msa_device_body(const abpoa_hip_scoring_t *sc_in, int n_sets, con
                 pr.multiProcessorCount; }
         if (nb < 1 || n_sets > nb * n_cu) use_rounds = false;
         if (opt_env("ABPOA_HIP_VERBOSE")) fprintf(stderr,
-                "[abpoa-hip] all-rounds kernel: %s, %zu B dynamic + %d B static LDS per workgroup, %d workgroups per CU, " "backtrack window %d B\n",
-                use_rounds ? "on" : "off", rounds_lds, st_lds, nb, b_r.lds.bt_bytes_tail);
+                "[abpoa-hip] all-rounds kernel: %s, %zu B dynamic + %d B static LDS per workgroup, %d workgroups per CU, " "backtrack window %d B, helpers %s (%d + 3 x %d B)\n",
+                use_rounds ? "on" : "off", rounds_lds, st_lds, nb, b_r.lds.bt_bytes_tail, b_r.lds.te_on ? "under the row loop" : "after the row loop", b_r.lds.te_main, b_r.lds.te_w);
     }
 
     // ---- the whole progressive alignment, queued back to back (ABPOA_HIP_DEVSYNC=1: synchronise and report after every kernel)
@@ -681,6 +700,19 @@ static int run_msa_device_body(const abpoa_hip_scoring_t *sc_in, int n_sets, con
                     stats->fuse_ms += ms * tp[3] / tall;
                             for (int i = 0; i < 4; ++i) stats->rounds_mticks[i] = tp[i] / n_sets * 1e-6; stats->rounds_rows_share = tp[1] / tall;
                             stats->rounds_mean_over_max = n_sets > 0 && tmax > 0 ? tall / n_sets / tmax : 0; }
+            // how much of the kernel is its slowest set: per phase mean / p99 / max ticks of a set, and max over mean of the sets' totals
+            if (opt_env("ABPOA_HIP_VERBOSE") && n_sets > 0 && tall > 0) {
+                static const char *const ph_[4] = {"prepare", "rows", "backtrack", "fuse"};
+                std::vector<double> v_((size_t)n_sets);
+                for (int i = 0; i < 4; ++i) {
+                    for (int s = 0; s < n_sets; ++s) v_[s] = (double)hs_[s].t_phase[i];
+                    std::sort(v_.begin(), v_.end());
+                    fprintf(stderr, "[abpoa-hip] all-rounds kernel, M ticks per set, %-9s: mean %.3f  p99 %.3f  max %.3f\n", ph_[i], tp[i] / n_sets * 1e-6,
+                            v_[(size_t)std::min<long long>(n_sets - 1, (long long)n_sets * 99 / 100)] * 1e-6, v_[(size_t)n_sets - 1] * 1e-6);
+                }
+                fprintf(stderr, "[abpoa-hip] all-rounds kernel, set totals: mean %.3f M ticks, max %.3f M ticks, max / mean %.3f\n", tall / n_sets * 1e-6, tmax * 1e-6,
+                        tmax / (tall / n_sets));
+            }
         }
         stats->n_rounds = max_reads > 0 ? max_reads - 1 : 0; stats->device_s = t_done - t_queue;
     }

@@ -5,8 +5,8 @@
 // while whole sets differ by only ~4 %, so a set that advances on its own finishes in the time of the slowest SET, not in the sum of the per-round
 // maxima (measured: 201 M vs 163 M cycles of row loop + backtrack per set).
 // Shape: GT = 256 threads per read-set as in the graph kernels; the row loop and the backtrack are one-wavefront code (rows_fast.h, backtrack.h) and
-// run on wavefront 0 while the other three wait at the workgroup barrier (ABPOA_HIP_ONE_WAVE_PHASE turns the barriers inside those phases into plain
-// waits).  Hand-over between phases is through HBM exactly as between the separate kernels; all of it is written and read by this one workgroup
+// run on one wavefront while the other three wait at the workgroup barrier or, as helpers of the direction-plane backtrack, walk the rows the row loop has
+// already left (backtrack_dir.h, EARLY START; ABPOA_HIP_ONE_WAVE_PHASE turns the barriers inside those phases into plain waits).  Hand-over between phases is through HBM exactly as between the separate kernels; all of it is written and read by this one workgroup
 // (one CU, one L1), so a workgroup barrier with vmcnt(0) is all the ordering it needs.
 #define ABPOA_HIP_ONE_WAVE_PHASE 1
 #include "fast_tail.h"
@@ -37,20 +37,28 @@ __device__ __forceinline__ AlnDesc uniform_desc(const AlnDesc *g) {
 }
 // row loop, then global best + backtrack, on the calling wavefront; returns the clock between the two
 // (DIR: direction-plane arenas, rows_fast.h DirFmt / backtrack_dir.h -- what the device-resident driver uses whenever the penalties allow it)
+// prog: the progress word for the helpers of the backtrack (nullptr: one wavefront per backtrack); it is written only where they start early
 template <typename T, int GAP, bool DIR>
-__device__ __noinline__ long long rounds_rows(const int slot, const int s_) {
+__device__ __noinline__ long long rounds_rows(const int slot, const int s_, int *prog) {
     const DevBatch &b = g_rounds[UNI(slot)].b; const int s = UNI(s_);
     const AlnDesc d = uniform_desc(b.aln + s);
-    align_fast_rows<T, GAP, 1, false, DIR>(b, d, b.out + s);
+    if constexpr (DIR) {
+        if (prog && takes_dir(b, d) && dir_walk_early(b, d)) {      // the helpers' tables are clear before the first row: whoever touches them is behind the progress word
+            int bytes_, pm_off_; (void)spec_region(b, true, 0, bytes_, pm_off_);
+            int *pm_all = (int *)(lds_raw + b.lds.phase_off + pm_off_);
+            for (int t = threadIdx.x & 63; t < (SPEC_WK - 1) * SPEC_PM_ROWS; t += 64) pm_all[t] = 0;
+        } else prog = nullptr;
+        align_fast_rows<T, GAP, 1, false, DIR>(b, d, b.out + s, prog);
+    } else align_fast_rows<T, GAP, 1, false, DIR>(b, d, b.out + s);
     return (long long)__builtin_amdgcn_s_memtime();
 }
 // role 0: the wavefront that ran the row loop; role 1: a second wavefront of the workgroup that walks the lower half of the graph at the same time
-// (backtrack_dir.h); ctl: eight ints of static LDS; gen: the round
+// (backtrack_dir.h); ctl: eight ints of static LDS per wavefront, and behind them the row loop's progress word; gen: the round
 template <typename T, int GAP, bool DIR>
 __device__ __noinline__ void rounds_tail(const int slot, const int s_, const int role_, int *ctl, const int gen_) {
     const DevBatch &b = g_rounds[UNI(slot)].b; const int s = UNI(s_);
     const AlnDesc d = uniform_desc(b.aln + s);
-    align_fast_tail<T, GAP, DIR>(b, d, b.out + s, UNI(role_), ctl, UNI(gen_));
+    align_fast_tail<T, GAP, DIR>(b, d, b.out + s, UNI(role_), ctl, UNI(gen_), ctl + 8 * SPEC_WK);
 }
 
 template <int GAP>
@@ -64,8 +72,8 @@ __global__ void __launch_bounds__(GT, 4) poa_rounds_kernel(const int slot, const
     // Which wavefront runs the one-wave phases.  A workgroup's four wavefronts sit on the four SIMDs of its CU; if it were always wavefront 0, the
     // four workgroups of a CU would run their row loops on the same SIMD while the other three idle.  Each workgroup draws a ticket from a per-CU
     // counter and the wavefront on SIMD (ticket mod 4) does the work.
-    __shared__ int sh_simd[GW], sh_target, sh_walk[8 * SPEC_WK];      // sh_walk: hand-over between the wavefronts of a backtrack
-    if (tid < 8 * SPEC_WK) sh_walk[tid] = 0;
+    __shared__ int sh_simd[GW], sh_target, sh_walk[8 * SPEC_WK + 1];      // sh_walk: hand-over between the wavefronts of a backtrack; [8 SPEC_WK]: the row loop's progress word
+    if (tid < 8 * SPEC_WK + 1) sh_walk[tid] = 0;
     {
         const unsigned hwid = __builtin_amdgcn_s_getreg(63492);      // HW_REG_HW_ID: simd_id [5:4], cu_id [11:8], sh_id [12], se_id [15:13]
         if ((tid & 63) == 0) sh_simd[tid >> 6] = (int)((hwid >> 4) & 3);
@@ -81,6 +89,7 @@ __global__ void __launch_bounds__(GT, 4) poa_rounds_kernel(const int slot, const
     const bool pair = !(b.dbg & 1024);               // (ABPOA_HIP_DBG bit 10: one wavefront per backtrack, for comparison)
     for (int k = k_lo; k < n_reads; ++k) {
         const long long c0 = (long long)__builtin_amdgcn_s_memtime();
+        if (tid == 0) sh_walk[8 * SPEC_WK] = 0;             // (no row of this round is complete; the barrier behind the prepare phase publishes it)
         rounds_prepare(slot, s, k);
         __syncthreads();                                    // descriptor, row tables and predecessor lists of this round are complete
         if (ld_fresh(&st->status) != POA_ST_OK) break;      // capacity exceeded (or about to be): the set goes to the second pass / the host driver
@@ -92,13 +101,14 @@ __global__ void __launch_bounds__(GT, 4) poa_rounds_kernel(const int slot, const
             if ((flags & ALN_FAST_OK) && !(b.lds.wide_nw >= 1 && w >= b.lds.wide_w_lo && w <= b.lds.wide_w_hi)) {
                 bool done_dir = false;
                 if constexpr (GAP != 0) if (b.dir_mode) {      // (linear gaps keep H records: no direction words)
-                    if (bits == 16) { c2 = rounds_rows<int16_t, GAP, true>(slot, s); rounds_tail<int16_t, GAP, true>(slot, s, pair ? 0 : -1, sh_walk, k); }
-                    else { c2 = rounds_rows<int32_t, GAP, true>(slot, s); rounds_tail<int32_t, GAP, true>(slot, s, pair ? 0 : -1, sh_walk, k); }
+                    int *prog = pair ? sh_walk + 8 * SPEC_WK : nullptr;
+                    if (bits == 16) { c2 = rounds_rows<int16_t, GAP, true>(slot, s, prog); rounds_tail<int16_t, GAP, true>(slot, s, pair ? 0 : -1, sh_walk, k); }
+                    else { c2 = rounds_rows<int32_t, GAP, true>(slot, s, prog); rounds_tail<int32_t, GAP, true>(slot, s, pair ? 0 : -1, sh_walk, k); }
                     done_dir = true;
                 }
                 if (done_dir) {}
-                else if (bits == 16) { c2 = rounds_rows<int16_t, GAP, false>(slot, s); rounds_tail<int16_t, GAP, false>(slot, s, -1, sh_walk, k); }
-                else { c2 = rounds_rows<int32_t, GAP, false>(slot, s); rounds_tail<int32_t, GAP, false>(slot, s, -1, sh_walk, k); }
+                else if (bits == 16) { c2 = rounds_rows<int16_t, GAP, false>(slot, s, nullptr); rounds_tail<int16_t, GAP, false>(slot, s, -1, sh_walk, k); }
+                else { c2 = rounds_rows<int32_t, GAP, false>(slot, s, nullptr); rounds_tail<int32_t, GAP, false>(slot, s, -1, sh_walk, k); }
             } else if ((tid & 63) == 0) b.out[s].status = ABPOA_HIP_EINVAL;       // -> poa_fuse_body marks the set for the fall-back
         } else if (GAP != 0 && b.dir_mode && pair) {      // the other three wavefronts: helpers of the backtrack (backtrack_dir.h)
             if constexpr (GAP != 0) {

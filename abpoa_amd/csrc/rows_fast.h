@@ -60,6 +60,7 @@ template <typename T> struct FastIO {
     GLOBAL_AS const uint8_t *row_base, *row_sdist; GLOBAL_AS const int32_t *row_remain, *pred_off, *pred_row;
     GLOBAL_AS int32_t *g_bsn, *g_esn, *row_max_i, *g_left, *g_right; GLOBAL_AS int64_t *g_coff;
     T *planes;
+    int prog_a;      // all-rounds kernel, helpers of the backtrack under the row loop (backtrack_dir.h): LDS byte address of the progress word, -1: none
 };
 
 // literal SIMD_SET_F for the vectors [nfast, ...) of one 64-lane chunk (global mode), reference :859-875 / :978-997
@@ -1310,6 +1311,12 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             const int rb = t0 - 64 + lane; if (wid == 0) { io.g_bsn[rb] = vg_geo & 0xfff; io.g_esn[rb] = (vg_geo >> 12) & 0xfff; io.g_coff[rb] = (long long)(uint32_t)vg_off * PN;
                     io.row_max_i[rb] = vg_mi; }
             if (rb >= 1) n_vec_lane += ((vg_geo >> 12) & 0xfff) - (vg_geo & 0xfff) + 1;
+            // progress word (backtrack_dir.h): rows below t0 are complete -- their direction words and the geometry above have been acknowledged.  Once per tile,
+            // here, where the metadata loads of switch_tile() are about to wait for the same counter; nothing in the per-row path.
+            if constexpr (DIR && NW == 1 && !WIDEB) if (io.prog_a >= 0) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                *(volatile lds_int_t *)(size_t)(unsigned)io.prog_a = t0;
+            }
         }
         switch_tile(t0);
 #ifdef ABPOA_HIP_ROW_CENSUS
@@ -1564,9 +1571,11 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
 // The fast path is two kernels -- row loop, then global best + backtrack -- so that the row loop's register allocation
 // (its SGPR budget above all) is not shared with the tail; the hand-over is the AlnOut record in HBM.
 template <typename T, int GAP, int NW = 1, bool WIDEB = false, bool DIR = false, bool XL = false>
-__device__ __forceinline__ void align_fast_rows(const DevBatch &b, const AlnDesc &d, AlnOut *out_rec) {
+__device__ __forceinline__ void align_fast_rows(const DevBatch &b, const AlnDesc &d, AlnOut *out_rec, const int *prog = nullptr) {
     const int lane = threadIdx.x & 63;
+    typedef __attribute__((address_space(3))) int lds_int_t;
     FastIO<T> io;
+    io.prog_a = -1; if (prog) { io.prog_a = (int)(unsigned)(size_t)(lds_int_t *)prog; asm("" : "+v"(io.prog_a)); }
     io.row_base = vgpr_ptr(b.row_base + d.row0); io.row_remain = vgpr_ptr(b.row_remain + d.row0); io.row_sdist = vgpr_ptr((DIR ? b.row_sdist : b.row_base) + d.row0);
     io.pred_off = vgpr_ptr(b.pred_off + d.poff0); io.pred_row = vgpr_ptr(b.pred_row + d.pred0);
     io.g_bsn = vgpr_ptr(b.dp_beg_sn + d.row0); io.g_esn = vgpr_ptr(b.dp_end_sn + d.row0); io.row_max_i = vgpr_ptr(b.row_max_i + d.row0);
@@ -1591,6 +1600,11 @@ __device__ __forceinline__ void align_fast_rows(const DevBatch &b, const AlnDesc
     if (NW > 1 ? threadIdx.x == 0 : lane == 0) { GLOBAL_AS AlnOut *o = vgpr_ptr(out_rec); o->status = status; o->n_cells = n_cells; o->cells_used = cursor; o->clk_dp = clk1 - clk0;
             o->n_rows_done = rows_done; for (int i_ = 0; i_ < 6; ++i_) o->seg[i_] = fseg[i_];
             if (b.align_mode == ABPOA_HIP_EXTEND_MODE) { o->best_score = best3[0]; o->best_row = best3[1]; o->best_col = best3[2]; } }
+    // every way out of the row loop ends the progress word: rows up to last_done are complete, or -1 after a status (backtrack_dir.h SPEC_PROG_*)
+    if (io.prog_a >= 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        *(volatile lds_int_t *)(size_t)(unsigned)io.prog_a = status == 0 ? ((last_done + 1) | (1 << 30)) : -1;
+    }
 }
 
 
