@@ -59,14 +59,17 @@ long long g_dbg[10] = {0};
 long long g_dir_counts[2] = {0, 0};      // alignments whose backtrack walked a direction plane; alignments redone with score records (NEED_SCORES)
 
 int engine_device() { return g.ready ? g.device : -1; }
+int device_cu_count(int device) {
+    hipDeviceProp_t pr;
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return 256;
+    return (hipGetDeviceProperties(&pr, device) == hipSuccess && pr.multiProcessorCount > 0) ? pr.multiProcessorCount : 256;
+}
 void add_global_stats(const StreamStats &s) {
     std::lock_guard<std::mutex> lk(g.stats_mu);
     g.stats.n_launches += s.n_launches; g.stats.n_alignments += s.n_alignments; g.stats.n_cells += s.n_cells;
     g.stats.algo_bytes += s.algo_bytes; g.stats.kernel_ms += s.kernel_ms; g.stats.h2d_ms += s.h2d_ms; g.stats.d2h_ms += s.d2h_ms; g.stats.tail_ms += s.tail_ms; g.stats.rounds_ms += s.rounds_ms;
     g.stats.rounds_launches += s.rounds_launches; g.stats.rounds_algo_bytes += s.rounds_algo_bytes;
 }
-
-static size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
 // ------------------------------------------------------------------------------------------------ BatchStream
 int BatchStream::open(int device) {
@@ -84,112 +87,6 @@ void BatchStream::close() {
     for (auto &e : ev_) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(stream_);
     open_ = false;
-}
-
-// LDS carve-up of one wavefront (engine.h LdsPlan) for a launch whose largest query is max_qlen, widest score type max_bits
-// and widest expected band est_cols columns.
-// (-DABPOA_HIP_WIDE_W3, experiment: three wavefronts per SIMD in the wide loop -- twelve workgroups per CU, ring depth down to 2)
-#ifdef ABPOA_HIP_WIDE_W3
-constexpr int WIDE_PER_CU_MAX = 12, WIDE_RING_MIN = 2;
-#else
-constexpr int WIDE_PER_CU_MAX = 8, WIDE_RING_MIN = 4;
-#endif
-void make_lds_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max_bits, int64_t est_cols, int n_aln, LdsPlan *Lp) {
-    LdsPlan &L = *Lp;
-    const int P = sc->gap_mode == ABPOA_HIP_LINEAR_GAP ? 1 : (sc->gap_mode == ABPOA_HIP_AFFINE_GAP ? 3 : 5);
-    const int cell = max_bits / 8, npr = P == 1 ? 1 : (P == 3 ? 2 : 3);
-    // query codes in LDS: up to 32000 bases keep the fast row loops (their per-row registers hold band vectors in 12 bits: 4095 x 8 columns);
-    // longer reads take the general kernel.  Above 16 K bases the kernels may use up to 62 KB of LDS per wavefront instead of 36 - 38 KB.
-    const bool longq = max_qlen + 1 > 16384;
-    L.q_off = 0; L.q_cap = max_qlen + 1 <= 32000 ? (int)align_up(max_qlen + 1, 16) : 0;
-    L.mat_off = L.q_cap; L.mx_off = L.mat_off + (int)align_up(4 * sc->m * sc->m, 16);
-    L.phase_off = L.mx_off + (int)align_up(4 * sc->m * (sc->m + 1), 16);
-    L.ring_off = lds_fixed_bytes_dp(); L.ring_rows = 16; L.ring_cols = (int)align_up((size_t)est_cols, 64);
-    while ((int64_t)L.ring_rows * npr * L.ring_cols * cell > 40 * 1024 && L.ring_rows > 4) L.ring_rows /= 2;
-    if ((int64_t)L.ring_rows * npr * L.ring_cols * cell > 40 * 1024) L.ring_cols = 0;     // rows too wide: HBM path only
-    const int ring_bytes = L.ring_rows * npr * L.ring_cols * cell;
-    L.bt_off = lds_fixed_bytes_bt();
-    // staged arena window of the backtrack: 24 KB, less when a long query already takes much of the 40 KB a workgroup may use
-    L.bt_bytes = std::max(std::max(8 * 1024, std::min(24 * 1024, (longq ? 62 : 38) * 1024 - L.phase_off - L.bt_off)), L.ring_off + ring_bytes - L.bt_off) & ~15;
-    // fast row loop: packed score ring (words per cell: linear 1, int16 affine 1, int16 convex 2, int32 affine 2, int32 convex 3)
-    const int fw = P == 1 ? 1 : (max_bits == 16 ? (P == 3 ? 1 : 2) : (P == 3 ? 2 : 3));      // (linear gaps: H alone)
-    L.fr_off = 0; L.fr_rows = 16; L.fr_cols = fw ? std::max(128, (int)align_up((size_t)est_cols, 64)) : 0;      // >= 128: the turbo row pads one chunk unconditionally
-    const int fr_budget = (longq ? 62 : 36) * 1024 - L.phase_off;
-    while (L.fr_cols && (int64_t)L.fr_rows * fw * (L.fr_cols + 4) * 4 + 64 > fr_budget && L.fr_rows > 4) L.fr_rows /= 2;
-    if (L.fr_cols && (int64_t)L.fr_rows * fw * (L.fr_cols + 4) * 4 + 64 > fr_budget) L.fr_cols = 0;
-    if (L.q_cap == 0 || est_cols > 1024) L.fr_cols = 0;
-    { const char *nf_ = opt_env("ABPOA_HIP_NOFAST"); if (nf_ && atoi(nf_)) L.fr_cols = 0; }
-    const int fr_bytes = L.fr_cols ? L.fr_rows * fw * (L.fr_cols + 4) * 4 + 64 : 0;
-    L.total = L.phase_off + std::max(std::max(L.ring_off + ring_bytes, L.bt_off + L.bt_bytes), L.fr_off + fr_bytes);
-    // the fast path's tail kernel: its own window size -- 28 KB, less when a long query already takes much of the 38 (62) KB that let four (two) of
-    // its workgroups share a CU; the general kernel's bt_bytes above also covers its score ring and would halve that residency
-    L.bt_bytes_tail = std::max(8 * 1024, std::min(28 * 1024, (longq ? 62 : 38) * 1024 - L.phase_off - L.bt_off)) & ~15;
-    // a launch with fewer alignments than 4 per CU can afford a larger window per workgroup (fewer window reloads on wide bands): 160 KB / CU
-    // divided by the workgroups a CU has to hold, capped at 56 KB
-    { const int per_cu = std::max(1, (n_aln + 255) / 256);
-      if (per_cu < 4 && L.fr_cols > 128) L.bt_bytes_tail = std::max(L.bt_bytes_tail, std::min(56 * 1024, 160 * 1024 / per_cu - 2048 - L.phase_off - L.bt_off) & ~15); }
-    // more alignments than a GPU holds tail workgroups at the 24 KB window (4 per CU): a 12 KB window doubles the residency, and the tail kernel of such
-    // a launch runs in as many turns as it has workgroups per resident set (8000 x 1 kb alignments: tail 153 -> 127 ms per step)
-    if (n_aln > 4 * 256 && L.fr_cols && L.fr_cols <= 128) L.bt_bytes_tail = std::min(L.bt_bytes_tail, 12 * 1024);
-    { const char *tb_ = opt_env("ABPOA_HIP_BT_BYTES"); if (tb_ && atoi(tb_) >= 4096 && atoi(tb_) <= 65536) L.bt_bytes_tail = atoi(tb_) & ~15; }
-    L.total_rows = L.phase_off + L.fr_off + fr_bytes; L.total_tail = L.phase_off + L.bt_off + L.bt_bytes_tail;
-    L.te_on = L.te_main = L.te_w = 0;      // (the all-rounds kernel's split of the backtrack region: msa_device.cpp decides it where that kernel runs)
-    L.bt_wc = 0; { const char *wc_ = opt_env("ABPOA_HIP_BT_WC"); if (wc_ && atoi(wc_) >= 8 && atoi(wc_) <= 64) L.bt_wc = atoi(wc_) & ~7; }
-    // local row loop (rows_local.h): unbanded local alignments of at most 9 x 64 columns, int16; ring depth by what 60 KB hold
-    L.loc_rows = L.loc_cols = L.total_local = 0;
-    if (sc->align_mode == ABPOA_HIP_LOCAL_MODE && sc->wb < 0 && P != 1 && L.q_cap && !(opt_env("ABPOA_HIP_NOFAST") && atoi(opt_env("ABPOA_HIP_NOFAST")))) {
-        const int lw = P == 3 ? 1 : 2;                 // ring words per column (int16: H | E1 packed, E2)
-        L.loc_cols = 9 * 64; L.loc_rows = 16;
-        while ((int64_t)L.loc_rows * lw * (L.loc_cols + 4) * 4 > 60 * 1024 - L.phase_off && L.loc_rows > 4) L.loc_rows /= 2;
-        L.total_local = L.phase_off + L.fr_off + (int)align_up((size_t)L.loc_rows * lw * (L.loc_cols + 4) * 4, 16) + 256;      // (+ the team kernel's exchange slots: 2 x 4 x 16 bytes)
-    }
-    // wide row loop (dp_wide_rows.hip): alignments whose band half-width w is in [wide_w_lo, wide_w_hi] -- rows of 2..7 chunks of 64 columns --
-    // go to the kernel that keeps every chunk of a row in registers; it has its own score ring (448 columns; depth by what fits:
-    // predecessors up to 15 rows back are common in a graph of noisy reads).  ABPOA_HIP_NOWIDE=1 turns it off, ABPOA_HIP_RING_ROWS sets
-    // the depth, ABPOA_HIP_TEAM=1|2|4 sets the wavefronts per alignment.
-    L.wide_nw = 0; L.wfr_rows = L.wfr_cols = L.wx_off = L.total_wide = 0; L.wide_w_lo = 1; L.wide_w_hi = 0; L.narrow_off = 0; L.w_mx_off = L.w_phase_off = 0;
-    { const char *nw_ = opt_env("ABPOA_HIP_NOWIDE"), *mw_ = opt_env("ABPOA_HIP_TEAM");
-      if (L.fr_cols && L.q_cap && !(nw_ && atoi(nw_))) {
-          // wavefronts per alignment: 1.  Teams of 2 / 4 (ABPOA_HIP_TEAM=2|4, dp_team_rows.hip) give identical results but are slower on gfx950
-          // as measured (3.9 k vs 3.1 k cycles per 5-chunk row): a row's ~370 instructions of scalar bookkeeping are repeated by every wavefront
-          // of the team and outweigh the ~28 instructions per chunk that the split saves (profiles/r2_team_vs_single.txt).
-          L.wide_nw = 1;
-          if (mw_ && (atoi(mw_) == 1 || atoi(mw_) == 2 || atoi(mw_) == 4)) L.wide_nw = atoi(mw_);
-          // (rows wider than the 448-column ring -- reads of 20 kb and more: w = 10 + 0.01 L -- take the kernel's long-read form: 704 columns, 8 - 11 chunks a row)
-          L.wfr_cols = (est_cols > WIDE_RING_COLS && !(opt_env("ABPOA_HIP_NOXL") && atoi(opt_env("ABPOA_HIP_NOXL")))) ? WIDE_RING_COLS_XL : WIDE_RING_COLS; L.wfr_rows = 16;
-          if (sc->m > 16) L.wide_nw = 0;      // (4-bit query codes)
-          L.w_mx_off = (int)align_up((size_t)(max_qlen + 2) / 2, 16); L.w_phase_off = L.w_mx_off + (int)align_up(4 * sc->m * (sc->m + 1), 16);
-          // ring words per column of the wide kernels: as the narrow loop's, but two instead of three for convex int32 (rows_fast.h EPACK: E as 16-bit
-          // differences to H, which needs gap-open + extend <= 65535)
-          const int fww = (P == 5 && max_bits == 32) ? 2 : fw;
-          if (P == 5 && (sc->gap_open1 + sc->gap_ext1 >= 65535 || sc->gap_open2 + sc->gap_ext2 >= 65535)) L.wide_nw = 0;      // (0xffff: "E is inf" in the compact spill records)
-          L.wide_w_lo = 40; L.wide_w_hi = (L.wfr_cols - 2 * 8 - 1) / 2;
-          { const char *lo_ = opt_env("ABPOA_HIP_WIDE_LO"); if (lo_ && atoi(lo_) > 0) L.wide_w_lo = atoi(lo_); }
-          const char *rr_env_ = opt_env("ABPOA_HIP_RING_ROWS");
-          if (rr_env_ && atoi(rr_env_) >= 4) L.wfr_rows = atoi(rr_env_) >= 16 ? 16 : (atoi(rr_env_) >= 8 ? 8 : 4); else rr_env_ = nullptr;
-          // (up to 120 KB per wavefront: a convex int32 ring of 16 rows is 58 KB; above 64 KB the launch raises the kernel's dynamic-LDS limit)
-          const int budget = 120 * 1024 - L.w_phase_off - 512;
-          while ((int64_t)L.wfr_rows * fww * (L.wfr_cols + 4) * 4 > budget && L.wfr_rows > 4) L.wfr_rows /= 2;
-          // One wavefront per alignment: LDS is what limits how many alignments a CU holds.  It is handed out in pieces of 1280 B, 128 per CU
-          // (tools/probes/lds_granule.hip: 3 x 53760 B fit a CU, 3 x 54080 B do not, whatever the occupancy query says).  The deepest ring with which
-          // the whole launch is resident, counting at most eight workgroups per CU -- two wavefronts per SIMD, which is what the registers allow and
-          // what pays: a SIMD with two alignments to issue from does 1.6x the rows of one with a single wavefront (tools/two_waves_probe.py).  A
-          // shallower ring sends more rows to the HBM gather (predecessor older than the ring: 0.5 % / 14 % / ~45 % of the rows of a 15 %-error
-          // graph at depth 16 / 8 / 4; rows +1.6 % / +6.5 %).
-          const int extra_ = L.wide_nw > 1 ? 16 * 16 + 64 : 0;      // (exchange slots: teams only)
-          auto per_cu_ = [&](int rows_) { return std::min<int64_t>(WIDE_PER_CU_MAX, 128 / ((L.w_phase_off + (int64_t)rows_ * fww * (L.wfr_cols + 4) * 4 + extra_ + 1279) / 1280)); };
-          if (!(rr_env_)) {
-              const int top_ = L.wfr_rows; int best_ = top_;
-              for (int r_ = top_; r_ >= WIDE_RING_MIN; r_ /= 2) {
-                  if (per_cu_(r_) > per_cu_(best_)) best_ = r_;
-                  if (per_cu_(r_) * 256 >= std::min(n_aln, WIDE_PER_CU_MAX * 256)) { best_ = r_; break; }
-              }
-              L.wfr_rows = best_;
-          }
-          L.wx_off = L.fr_off + (int)align_up((size_t)L.wfr_rows * fww * (L.wfr_cols + 4) * 4, 16);
-          L.total_wide = L.w_phase_off + L.wx_off + extra_;
-          if (P == 1) L.wide_nw = 0;      // (linear gaps: the narrow loop only -- dp_common.h takes_fast)
-      } }
 }
 
 int BatchStream::prepare(const abpoa_hip_scoring_t *sc, int n, const BatchShape *sh, unsigned flags) {
@@ -210,14 +107,14 @@ int BatchStream::prepare(const abpoa_hip_scoring_t *sc, int n, const BatchShape 
         d.query_off = q_tot_; d.row0 = rows_tot_; d.poff0 = rows_tot_ + i; d.pred0 = preds_tot_; d.out0 = outs_tot_; d.cigar_off = cig_tot_;
         q_tot_ += d.qlen; rows_tot_ += d.n_rows; preds_tot_ += sh[i].n_pred; outs_tot_ += sh[i].n_out; cig_tot_ += d.cigar_cap;
         const int pn = d.bits == 16 ? 16 : 8;
-        const int64_t width = (int64_t)((d.qlen + pn) / pn) * pn;
+        const int64_t width = padded_width(d.qlen, pn);
         // values per DP column in the arena: P planes (general kernel) or one padded cell record (fast loop: 4 / 8 values)
         // (linear gaps: one plane in the general kernel, {H, match flag} in the fast loops)
-        const int pv = sc->gap_mode == ABPOA_HIP_LINEAR_GAP ? 2 : (sc->gap_mode == ABPOA_HIP_AFFINE_GAP ? 4 : 8);
+        const int pv = record_values(sc->gap_mode);
         full_cells_[i] = width * pv * d.n_rows;
-        int64_t est = banded ? std::min<int64_t>(width, 2LL * d.w + 3 * pn + 32) : width;
+        int64_t est = band_cols(width, d.w, pn, banded);
         // (tests: force the overflow -> full-width retry path)
-        { const char *pct_ = opt_env("ABPOA_HIP_ARENA_PCT"); if (pct_ && atoi(pct_) > 0 && atoi(pct_) < 100) est = std::max<int64_t>(pn, est * atoi(pct_) / 100); }
+        { const int pct_ = opt_int("ABPOA_HIP_ARENA_PCT", 0); if (pct_ > 0 && pct_ < 100) est = std::max<int64_t>(pn, est * pct_ / 100); }
         d.plane_cap = std::min<int64_t>(full_cells_[i], width * pv + est * pv * (d.n_rows - 1));
         est_cells_[i] = d.plane_cap;
         // direction-plane arenas (dir_plane.h; run() decides whether a pass uses them): words of DB bytes per column for every row, score records for the
@@ -271,9 +168,8 @@ int BatchStream::run() {
     // direction-plane arenas for the fast row loops (dir_plane.h) unless the caller wants the score planes back (trace), the penalties do not fit the
     // words, or ABPOA_HIP_NODIR=1; an alignment whose backtrack meets the one case the words cannot decide is redone with score records
     // (tests: ABPOA_HIP_DIRTRACE=1 keeps the direction plane in trace mode; the trace then carries the WORDS of every cell in plane 0)
-    const bool dirtrace = trace && opt_env("ABPOA_HIP_DIRTRACE") && atoi(opt_env("ABPOA_HIP_DIRTRACE"));
-    bool dir = (!trace || dirtrace) && banded && sc->align_mode == ABPOA_HIP_GLOBAL_MODE && dir_plane_usable(sc->gap_mode, sc->gap_open1, sc->gap_ext1, sc->gap_open2, sc->gap_ext2) &&
-               !(opt_env("ABPOA_HIP_NODIR") && atoi(opt_env("ABPOA_HIP_NODIR"))) && !(opt_env("ABPOA_HIP_TEAM") && atoi(opt_env("ABPOA_HIP_TEAM")) > 1);
+    const bool dirtrace = trace && opt_on("ABPOA_HIP_DIRTRACE");
+    bool dir = (!trace || dirtrace) && banded && sc->align_mode == ABPOA_HIP_GLOBAL_MODE && dir_words_allowed(sc);
     // alignment-level eligibility for the register-resident row loop: every row active, band state at its reset value
     for (int i = 0; i < n; ++i) {
         AlnDesc &d = desc_[i]; bool ok = banded || (sc->align_mode == ABPOA_HIP_LOCAL_MODE && sc->wb < 0);      // (unbanded local: the local row loop; band state is not used)
@@ -316,8 +212,8 @@ int BatchStream::run() {
             int max_qlen = 0, max_bits = 16; int64_t est_cols = 0;
             for (const AlnDesc &d : pass) {
                 max_qlen = std::max(max_qlen, d.qlen); max_bits = std::max(max_bits, d.bits);
-                const int pn = d.bits == 16 ? 16 : 8; const int64_t width = (int64_t)((d.qlen + pn) / pn) * pn;
-                est_cols = std::max<int64_t>(est_cols, banded ? std::min<int64_t>(width, 2LL * d.w + 3 * pn + 32) : width);
+                const int pn = d.bits == 16 ? 16 : 8;
+                est_cols = std::max<int64_t>(est_cols, band_cols(padded_width(d.qlen, pn), d.w, pn, banded));
             }
             make_lds_plan(sc, max_qlen, max_bits, est_cols, (int)pass.size(), &b.lds);
             for (const AlnDesc &d : pass) b.bits_mask |= d.bits == 16 ? 1 : 2;
@@ -329,13 +225,13 @@ int BatchStream::run() {
         if (b.lds.wide_nw > 1) dir = false;
         // (ABPOA_HIP_DIR_WIDE=1: words for the wide-band alignments too -- the device-resident driver does that by itself when the record arenas of a
         //  job do not fit the device; here it is a test switch)
-        const bool dir_wide = dir && opt_env("ABPOA_HIP_DIR_WIDE") && atoi(opt_env("ABPOA_HIP_DIR_WIDE")) > 0;
+        const bool dir_wide = dir && opt_int("ABPOA_HIP_DIR_WIDE", 0) > 0;
         for (size_t t = 0; t < todo.size(); ++t) {
             AlnDesc &d = desc_[todo[t]];
             // direction-plane arenas for the narrow-band alignments of a dir pass; the wide-band ones keep score records (dp_common.h takes_dir / takes_wide)
             // (an alignment the general kernel will run -- seeded band of the -s retry, a row with more predecessors than a word names, no fast row loop in the
             //  plan -- stores its planes: the records' estimate, not the words'; host mirror of dp_common.h takes_fast)
-            const int dbg_ = opt_env("ABPOA_HIP_DBG") ? atoi(opt_env("ABPOA_HIP_DBG")) : 0;
+            const int dbg_ = opt_int("ABPOA_HIP_DBG", 0);
             const bool fast_a = (d.flags & ALN_FAST_OK) && fast_global_job(sc->gap_mode, sc->align_mode, sc->wb, sc->gap_ext1) && fast_global_aln(sc->gap_mode, d.w, d.pad0) &&
                                 b.lds.fr_cols > 0 &&
                                 d.qlen <= b.lds.q_cap && !(dbg_ & 64);
@@ -351,7 +247,7 @@ int BatchStream::run() {
         b.want_trace = trace ? 1 : 0; b.fresh_band = fresh ? 1 : 0;
         b.dir_mode = dir ? (dir_wide ? 2 : 1) : 0; b.row_sdist = di + o_sdist_; b.row_pd = (const uint32_t *)(di + o_pd_);
         b.want_lr = (trace || (flags_ & BS_WANT_BAND_STATE)) ? 1 : 0;
-        { const char *dbg_ = opt_env("ABPOA_HIP_DBG"); b.dbg = dbg_ ? atoi(dbg_) : 0; }
+        b.dbg = opt_int("ABPOA_HIP_DBG", 0);
         b.mat = (const int32_t *)(di + o_mat_); b.aln = (const AlnDesc *)(di + o_desc_); b.out = (AlnOut *)(dout + o_rec_);
         b.query = di + o_query_; b.row_base = di + o_base_; b.row_node_id = (const int32_t *)(di + o_nid_); b.row_remain = (const int32_t *)(di + o_rem_);
         b.row_active = di + o_act_; b.pred_off = (const int32_t *)(di + o_poff_); b.pred_row = (const int32_t *)(di + o_pred_);
@@ -527,23 +423,12 @@ void abpoa_hip__dir_counts(long long *out) { out[0] = __atomic_exchange_n(&g_dir
 //  workgroups per CU by the 1280-byte allocation granule of gfx950, the wide kernels' phase offset, the band half-widths [lo, hi] that take it)
 void abpoa_hip__wide_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max_bits, int n_aln, int *out) {
     abpoa_hip::LdsPlan L; const int pn = max_bits == 16 ? 16 : 8; const int w = sc->wb + (int)(sc->wf * (float)max_qlen);
-    abpoa_hip::make_lds_plan(sc, max_qlen, max_bits, std::min<int64_t>((int64_t)((max_qlen + pn) / pn) * pn, 2LL * w + 3 * pn + 32), n_aln, &L);
-    out[0] = L.wide_nw; out[1] = L.wfr_rows; out[2] = L.total_wide; out[3] = L.total_wide > 0 ? std::min(WIDE_PER_CU_MAX, 128 / ((L.total_wide + 1279) / 1280)) : 0;
+    abpoa_hip::make_lds_plan(sc, max_qlen, max_bits, abpoa_hip::band_cols(abpoa_hip::padded_width(max_qlen, pn), w, pn, true), n_aln, &L);
+    out[0] = L.wide_nw; out[1] = L.wfr_rows; out[2] = L.total_wide; out[3] = L.total_wide > 0 ? abpoa_hip::wide_workgroups_per_cu(L.total_wide) : 0;
     out[4] = L.w_phase_off; out[5] = L.wide_w_lo; out[6] = L.wide_w_hi;
 }
 void abpoa_hip__debug_clocks(long long *out) { for (int i = 0; i < 10; ++i) { out[i] = g_dbg[i]; g_dbg[i] = 0; } }
 void abpoa_hip_reset_stats(void) { std::lock_guard<std::mutex> lk(g.stats_mu); memset(&g.stats, 0, sizeof(g.stats)); }
-
-// reference src/simd_abpoa_align.c:1672-1683
-int abpoa_hip_score_bits(const abpoa_hip_scoring_t *sc, int n_rows, int qlen, int32_t *inf_min) {
-    int oe1 = sc->gap_open1 + sc->gap_ext1, oe2 = sc->gap_open2 + sc->gap_ext2;
-    int len = qlen > n_rows ? qlen : n_rows;
-    int max_score = std::max(qlen * sc->max_mat, len * sc->gap_ext1 + sc->gap_open1);
-    int bits, lo;
-    if (max_score <= INT16_MAX - sc->min_mis - oe1 - oe2) { bits = 16; lo = INT16_MIN; } else { bits = 32; lo = INT32_MIN; }
-    if (inf_min) *inf_min = std::max(std::max(lo + sc->min_mis, lo + oe1), lo + oe2) + 31 * std::max(sc->gap_ext1, sc->gap_ext2);
-    return bits;
-}
 
 void abpoa_hip_free_result(abpoa_hip_result_t *r) {
     if (!r) return;

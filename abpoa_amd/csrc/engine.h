@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 #include "../../include/abpoa_hip.h"
+#include "dir_plane.h"
+#include "engine_options.h"
 
 namespace abpoa_hip {
 
@@ -133,9 +135,24 @@ __host__ __device__ inline bool fast_global_job(int gap_mode, int align_mode, in
 }
 __host__ __device__ inline bool fast_global_aln(int gap_mode, int w, int pad0) { return gap_mode != ABPOA_HIP_LINEAR_GAP || w + (pad0 >> 1) < LINEAR_FAST_W; }
 
+// Values per DP column in an arena of score records: one padded cell record of the fast loops (rows_fast.h FastFmt::CW) = the planes of the general kernel
+// (linear gaps: {H, match flag} in the fast loops, H alone in the general kernel)
+constexpr int record_values(int gap_mode) { return gap_mode == ABPOA_HIP_LINEAR_GAP ? 2 : (gap_mode == ABPOA_HIP_AFFINE_GAP ? 4 : 8); }
+// Columns a DP row is expected to take: the band of half-width w plus three vectors of pn cells and 32 columns of slack, the whole (padded) query without a band
+inline int64_t padded_width(int qlen, int pn) { return (int64_t)((qlen + pn) / pn) * pn; }
+inline int64_t band_cols(int64_t width, int w, int pn, bool banded) { const int64_t est = 2LL * w + 3 * pn + 32; return banded && est < width ? est : width; }
+// Direction words (dir_plane.h) instead of score records: what the penalties and the switches allow; each driver adds its own conditions
+inline bool dir_words_allowed(const abpoa_hip_scoring_t *sc) {
+    return dir_plane_usable(sc->gap_mode, sc->gap_open1, sc->gap_ext1, sc->gap_open2, sc->gap_ext2) && !opt_on("ABPOA_HIP_NODIR") && !(opt_int("ABPOA_HIP_TEAM", 0) > 1);
+}
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
 // Fixed LDS structures of the kernel (rows per metadata tile, ring depths); see dp_kernel.hip.
 int lds_fixed_bytes_dp();
 int lds_fixed_bytes_bt();
+// LDS carve-up of one launch and the wide row loop's workgroups per CU by its LDS (msa_device_plan.cpp: host arithmetic, no runtime call)
+void make_lds_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max_bits, int64_t est_cols, int n_aln, LdsPlan *L);
+int wide_workgroups_per_cu(int total_wide);
 
 // Launches the DP kernel for the whole batch on `stream`.
 hipError_t launch_dp(const DevBatch &b, int n_fast, hipStream_t stream, hipEvent_t after_rows);

@@ -35,7 +35,7 @@ const Row kTable[] = {
     {"ABPOA_HIP_NO_RAGGED_SPLIT", "T  1: read-sets with ragged read ends stay in the batch of the uniform ones (no all-rounds kernel for such a job)"},
     {"ABPOA_HIP_RAGGED_CONCURRENT", "T  1: the ragged batch of a mixed job runs on a second queue of the device beside the uniform batch (measured: see LOG.md)"},
     {"ABPOA_HIP_PASS_SETS", "T  read-sets per pass of the device-resident driver"},
-    {"ABPOA_HIP_FIRST_PASS", "T  start the node-slot ladder at pass 1 / 2 / 3 (profiling runs of one step)"},
+    {"ABPOA_HIP_FIRST_PASS", "T  start the node-slot ladder (3x, 4.5x, 6x, 4096x) at its second / third / fourth pass: 1 / 2 / 3 (profiling runs of one step)"},
     {"ABPOA_HIP_NO_PASS_HINT", "T  1: always start the ladder at 3x"},
     {"ABPOA_HIP_GROUPS", "T  read-set groups of the host driver"},
     {"ABPOA_HIP_ARENA_PCT", "T  arena estimate in percent (overflow-retry tests)"},
@@ -84,6 +84,9 @@ const char *opt_env(const char *name) {
     const int i = find(name);
     return (i >= 0 && cur->set[i]) ? cur->val[i].c_str() : nullptr;
 }
+bool opt_set(const char *name) { return opt_env(name) != nullptr; }
+bool opt_on(const char *name) { const char *e = opt_env(name); return e && atoi(e) != 0; }
+int opt_int(const char *name, int dflt) { const char *e = opt_env(name); return e ? atoi(e) : dflt; }
 
 int set_option(const char *name, const char *value) {
     const int i = name ? find(name) : -1;

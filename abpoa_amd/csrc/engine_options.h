@@ -5,11 +5,16 @@
 // the environment, overridden by abpoa_hip_set_option (include/abpoa_hip.h) -- which is how a host program or a test sets them without touching the
 // environment.  Code reads the snapshot through opt_env(name): the value string or nullptr, as getenv would give it, but stable for the whole call, identical
 // on every thread of the call, and nullptr for any name that is not in the table (a misspelt switch cannot steer anything).
+// The typed accessors below load the snapshot once per call, so a set_option on another thread cannot come between "is it set" and "what is its value".
+// A snapshot that set_option replaces is never freed (another thread's call may still read it): one small object leaks per changed switch.
 #pragma once
 
 namespace abpoa_hip {
 
-const char *opt_env(const char *name);      // value of a known switch in the current snapshot (nullptr: unset / unknown name)
+const char *opt_env(const char *name);      // value of a known switch in the current snapshot (nullptr: unset / unknown name); for switches read as strings
+bool opt_set(const char *name);             // the switch is present, whatever its value (ABPOA_HIP_VERBOSE=0 still prints)
+bool opt_on(const char *name);              // present and atoi(value) != 0
+int opt_int(const char *name, int dflt);    // atoi(value) when present, else dflt
 void refresh_options();                     // environment + overrides -> snapshot (every C-ABI entry calls it first)
 int set_option(const char *name, const char *value);      // override (value == nullptr: back to the environment); -1: unknown name
 int list_options(const char **names, const char **help, int cap);      // the table, for --help texts and the tests

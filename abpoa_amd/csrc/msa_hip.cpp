@@ -47,9 +47,7 @@ abpoa_hip_msa_timing_t g_timing;
 
 namespace abpoa_hip {
 namespace {
-bool env_on(const char *name) { const char *e = opt_env(name); return e && atoi(e) != 0; }
-int env_int(const char *name, int dflt) { const char *e = opt_env(name); return e ? atoi(e) : dflt; }
-bool strict_mode() { return env_on("ABPOA_HIP_STRICT"); }
+bool strict_mode() { return opt_on("ABPOA_HIP_STRICT"); }
 void free_all(abpoa_hip_msa_t *out, int n) { for (int s = 0; s < n; ++s) abpoa_hip_free_msa(&out[s]); }
 
 void add_stats(DeviceRunStats &t, const DeviceRunStats &d) {
@@ -92,14 +90,14 @@ PassOut device_passes(const abpoa_hip_scoring_t *sc, const abpoa_hip_readset_t *
     //  node slots are never what sends a set to the host driver; round-4 fuzzing: 22 of 813 sets, all for that reason -- protein sets at 15 % error)
     const double factors[4] = {3.0, 4.5, 6.0, 4096.0};
     constexpr int NPASS = 4;
-    const bool verbose = opt_env("ABPOA_HIP_VERBOSE") != nullptr;
+    const bool verbose = opt_set("ABPOA_HIP_VERBOSE");
     const int key = job_shape_key(sets, idx);
     int first_pass = 0;
     {   // (profiling runs of one step: start where a warmed-up process would)
-        const int fp = env_int("ABPOA_HIP_FIRST_PASS", 0);
+        const int fp = opt_int("ABPOA_HIP_FIRST_PASS", 0);
         if (fp >= 1 && fp < NPASS) first_pass = fp;
     }
-    if (!env_on("ABPOA_HIP_NO_PASS_HINT")) {
+    if (!opt_on("ABPOA_HIP_NO_PASS_HINT")) {
         std::lock_guard<std::mutex> lk(g_hint_mu);
         auto it = g_hint.find(key);
         if (it != g_hint.end()) first_pass = it->second;
@@ -120,7 +118,7 @@ PassOut device_passes(const abpoa_hip_scoring_t *sc, const abpoa_hip_readset_t *
             for (size_t i = 0; i < todo.size(); ++i) all_[i] = sets[todo[i]];
             const int res_ = msa_device_resident_sets(sc, (int)all_.size(), all_.data());
             if (res_ > 0 && chunk > (size_t)res_) chunk = (size_t)res_;
-            const int ps_ = env_int("ABPOA_HIP_PASS_SETS", 0);      // (tests: several passes on a small job)
+            const int ps_ = opt_int("ABPOA_HIP_PASS_SETS", 0);      // (tests: several passes on a small job)
             if (ps_ > 0 && chunk > (size_t)ps_) chunk = (size_t)ps_;
         }
         for (size_t at = 0; at < todo.size() && R.device_ok;) {
@@ -206,7 +204,7 @@ std::vector<int> device_list() {
 // uniform sets then keep the all-rounds kernel (narrow bands: one launch for all rounds, ~1.4x the lock-step launches' rate on 1 kb reads), which a job with a
 // single ragged set would lose for all of them.  (ABPOA_HIP_NO_RAGGED_SPLIT=1: one batch, as before round 5.)
 void split_ragged(std::vector<std::vector<int>> &batches, const abpoa_hip_scoring_t *sc, const abpoa_hip_readset_t *sets) {
-    if (!sc || sc->wb < 0 || sc->align_mode == ABPOA_HIP_LOCAL_MODE || env_on("ABPOA_HIP_NO_RAGGED_SPLIT")) return;
+    if (!sc || sc->wb < 0 || sc->align_mode == ABPOA_HIP_LOCAL_MODE || opt_on("ABPOA_HIP_NO_RAGGED_SPLIT")) return;
     std::vector<std::vector<int>> out_;
     for (auto &b_ : batches) {
         std::vector<int> uni, rag;
@@ -233,7 +231,7 @@ std::vector<std::vector<int>> deal_batches(const abpoa_hip_scoring_t *sc, const 
     std::vector<int> order(n_sets);
     for (int s = 0; s < n_sets; ++s) order[s] = s;
     std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] > cost[b]; });
-    const int per_q = std::max(1, env_int("ABPOA_GPU_BATCHES_PER_DEVICE", 2));
+    const int per_q = std::max(1, opt_int("ABPOA_GPU_BATCHES_PER_DEVICE", 2));
     // a batch should hold >= 1024 sets when the job allows: the device kernels run one wavefront per read-set, a GPU has 1024 SIMDs, and the
     // all-rounds kernel of the narrow-band jobs is at its best with ~1000 resident sets; never fewer batches than queues
     int nb = std::max(n_q, std::min(n_q * per_q, n_sets / 1024));
@@ -278,7 +276,7 @@ int msa_batch_impl(const abpoa_hip_scoring_t *sc_in, int n_sets, const abpoa_hip
         int n_q = (int)devs.size();
         const std::vector<std::vector<int>> batches = deal_batches(sc, sets, n_sets, n_q);
         // (experiment, ABPOA_HIP_RAGGED_CONCURRENT=1: the ragged batch of a mixed job on a second queue of the same device, beside the uniform batch's all-rounds kernel)
-        if (n_q == 1 && ctx_slot < 0 && batches.size() == 2 && env_on("ABPOA_HIP_RAGGED_CONCURRENT")) { devs.push_back(devs[0]); n_q = 2; }
+        if (n_q == 1 && ctx_slot < 0 && batches.size() == 2 && opt_on("ABPOA_HIP_RAGGED_CONCURRENT")) { devs.push_back(devs[0]); n_q = 2; }
         std::atomic<int> next{0};
         std::vector<PassOut> results(batches.size());
         std::vector<double> q_busy(n_q, 0.0);
@@ -315,7 +313,7 @@ int msa_batch_impl(const abpoa_hip_scoring_t *sc_in, int n_sets, const abpoa_hip
         }
         if (rc_dev != ABPOA_HIP_OK) { free_all(out, n_sets); return rc_dev; }
         if (n_q > 1) tot.device_s = tot.total_s = *std::max_element(q_busy.begin(), q_busy.end());      // queues ran side by side: the busiest one is the wall time
-        if (n_q > 1 && opt_env("ABPOA_HIP_VERBOSE")) {
+        if (n_q > 1 && opt_set("ABPOA_HIP_VERBOSE")) {
             fprintf(stderr, "[abpoa-hip] %d device queues, %zu batches; busy seconds per queue:", n_q, batches.size());
             for (int q = 0; q < n_q; ++q) fprintf(stderr, " dev%d %.3f", devs[q], q_busy[q]);
             fprintf(stderr, "\n");
@@ -332,7 +330,7 @@ int msa_batch_impl(const abpoa_hip_scoring_t *sc_in, int n_sets, const abpoa_hip
         tm.host_sort_s = tot.prepare_ms / 1e3; tm.host_fuse_s = tot.fuse_ms / 1e3;      // device kernels now: graph -> rows, cigar -> graph
         tm.n_host_sets = (int32_t)todo.size();                                          // how many sets take the host driver
         if (todo.empty()) return ABPOA_HIP_OK;
-        if (opt_env("ABPOA_HIP_VERBOSE"))
+        if (opt_set("ABPOA_HIP_VERBOSE"))
             fprintf(stderr, "[abpoa-hip] %zu of %d read-sets outgrew a device capacity: host driver for those\n", todo.size(), n_sets);
         if (strict_mode()) {
             free_all(out, n_sets);

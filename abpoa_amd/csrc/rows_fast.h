@@ -31,6 +31,7 @@ namespace abpoa_hip {
 // (vector-memory instruction issue, not bytes, is what a lone wave pays for).
 // (linear gaps, GAP == 0: {H, match flag})
 template <typename T, int GAP> struct FastFmt { static constexpr int CW = GAP == 0 ? 2 : (GAP == 1 ? 4 : 8); };
+static_assert(FastFmt<int, 0>::CW == record_values(ABPOA_HIP_LINEAR_GAP) && FastFmt<int, 1>::CW == record_values(ABPOA_HIP_AFFINE_GAP) && FastFmt<int, 2>::CW == record_values(ABPOA_HIP_CONVEX_GAP), "engine.h record_values");
 // Direction-plane arenas (DIR = true, dir_plane.h): a row owns ONE word per column -- 2 bytes (affine) or 4 (convex) -- that records every
 // decision the backtrack takes at that cell; only rows whose scores a later reader needs from HBM (a successor beyond the LDS score ring,
 // the global best at the sink's predecessors, a row too wide for the ring) also keep their cell records, IN FRONT of the words (a row's arena

@@ -107,5 +107,5 @@ def test_switches_form_one_table_and_nothing_else_reads_the_environment():
         text = open(fn).read()
         if not fn.endswith("engine_options.cpp"):
             assert "getenv(" not in text.replace("opt_env(", ""), f"{os.path.basename(fn)} reads the environment directly"
-            used |= set(re.findall(r'(?:opt_env|env_int|env_on)\("(ABPOA_[A-Z_0-9]+)"', text))
+            used |= set(re.findall(r'(?:opt_env|opt_set|opt_on|opt_int)\("(ABPOA_[A-Z_0-9]+)"', text))
     assert used <= set(table), f"switches read but not in the table: {sorted(used - set(table))}"
