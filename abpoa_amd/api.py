@@ -255,11 +255,11 @@ HOST_REASONS = ["other", "node slots at the first read", "predecessor-list slots
 def host_reasons(lib=None):
     """{reason: sets} for the read-sets the last msa_batch call handed to the host driver (abpoa_hip_get_host_reasons)."""
     lib = lib or ffi.lib()
-    a = (C.c_int32 * 12)()
+    a = (C.c_int32 * len(HOST_REASONS))()
     lib.abpoa_hip_get_host_reasons.argtypes = [C.POINTER(C.c_int32)]
     lib.abpoa_hip_get_host_reasons.restype = None
     lib.abpoa_hip_get_host_reasons(a)
-    return {HOST_REASONS[i]: int(a[i]) for i in range(12) if a[i]}
+    return {HOST_REASONS[i]: int(a[i]) for i in range(len(HOST_REASONS)) if a[i]}
 
 
 def format_output(result, names=None, out_cons=True, out_msa=False):

@@ -280,7 +280,7 @@ void fill_poa_dev(Job &J) {
     p.n_sets = J.n_sets; p.m = sc->m; p.max_mat = sc->max_mat; p.min_mis = sc->min_mis; p.o1 = sc->gap_open1; p.e1 = sc->gap_ext1; p.o2 = sc->gap_open2;
     p.e2 = sc->gap_ext2;
     p.wb = sc->wb; p.wf = sc->wf; p.gap_mode = sc->gap_mode; p.max_qlen = pl.max_qlen;
-    p.last_pass = pl.node_factor >= 6.0 ? 1 : 0;      // (msa_hip.cpp device_passes: 3x, 4.5x, 6x, 4096x; the 6x pass and the last)
+    p.last_pass = pl.node_factor >= 6.0 ? 1 : 0;      // (msa_passes.cpp run_pass_ladder: 3x, 4.5x, 6x, 4096x; the 6x pass and the last)
     p.in_cap = pl.in_cap; p.out_cap = pl.out_cap;
     p.dig_on = cigar_digest_on() ? 1 : 0;      // (tests: the fuse phase folds every graph cigar into PoaState.cigar_dig)
     // (the reference's own row order where the best cell is the FIRST row that reaches the maximum: local and extension mode, ref :1012-1026; the remaining
@@ -296,7 +296,7 @@ void fill_poa_dev(Job &J) {
     // (tests: graphs above this many nodes take the walks with tables in memory)
     { const int cap_ = opt_int("ABPOA_HIP_ORDER_CAP", -1); if (cap_ >= 0) p.order_lds = std::min(p.order_lds, cap_ & ~3); }
     // per-row records of the prepare kernel in LDS (5 bytes a row, 40 KB at most: four workgroups per CU still fit)
-    p.pad = pl.max_node_cap <= 8000 ? ((pl.max_node_cap + 3) & ~3) : 0;
+    p.lds_rows = pl.max_node_cap <= 8000 ? ((pl.max_node_cap + 3) & ~3) : 0;
     p.sets = (const PoaSet *)(di + L.o_sets); p.state = (PoaState *)(dg + L.o_state);
     p.read_off = (const int64_t *)(di + L.o_roff); p.read_len = (const int32_t *)(di + L.o_rlen); p.reads = di + L.o_reads;
     p.wts = J.any_w ? (const int32_t *)(di + L.o_wts) : nullptr;
@@ -401,7 +401,7 @@ void plan_rounds(Job &J) {
     if (use_rounds) {
         // (prepare: 5 bytes per row; fuse: 16 bytes per thread)
         auto dyn_of = [&](const DevBatch &x) { return std::max<size_t>(std::max<size_t>((size_t)x.lds.total_rows, (size_t)x.lds.total_tail),
-                std::max<size_t>((size_t)5 * (size_t)(p.pad > 0 ? p.pad : 0), (size_t)16 * 256)); };
+                std::max<size_t>((size_t)5 * (size_t)(p.lds_rows > 0 ? p.lds_rows : 0), (size_t)16 * 256)); };
         rounds_lds = dyn_of(b_r);
         int st_lds = 0; int nb = poa_rounds_residency(sc->gap_mode, rounds_lds, &st_lds);
         // four workgroups per CU when the job has that many sets: the kernel's static LDS (graph phases) comes out of the backtrack window
@@ -569,7 +569,7 @@ void fill_stats(const Job &J, DeviceRunStats *stats) {
 }
 
 // ---- stage 10: the results of the sets that finished; the others into `fallback`
-void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::vector<char> &need_fb, std::vector<int> *fallback, std::vector<int> *fallback_reason) {
+void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::vector<char> &need_fb, std::vector<SetFallback> *fallback) {
     const DevicePlan &pl = J.pl; Cache &C = *J.C; const Layout &L = J.L; const PoaDev &p = J.p; const uint8_t *hg = C.graph.host;
     const PoaState *hs = (const PoaState *)(hg + L.o_state);
     const int32_t *h_cnode = (const int32_t *)(hg + L.o_cnode), *h_ccov = (const int32_t *)(hg + L.o_ccov); const uint8_t *h_cbase = hg + L.o_cbase;
@@ -581,8 +581,8 @@ void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::
             // (only for a set that finished here: the record of a set that goes to another pass or to the host driver is overwritten there)
             if (pl.amb && hs[s].status == POA_ST_OK) { o_.is_rc = (uint8_t *)calloc((size_t)std::max(1, J.sets[s].n_reads), 1);
                     if (o_.is_rc) memcpy(o_.is_rc, hg + L.o_isrc + pl.ps[s].read0, (size_t)J.sets[s].n_reads); }
-            if (hs[s].status != POA_ST_OK) { need_fb[s] = hs[s].pad == 5 ? 2 : 1;
-                    if (J.dbg_sync) fprintf(stderr, "[poa-device] set %d falls back to the host driver: reason %d, %d nodes of %d\n", s, hs[s].pad,
+            if (hs[s].status != POA_ST_OK) { need_fb[s] = 1;
+                    if (J.dbg_sync) fprintf(stderr, "[poa-device] set %d falls back to the host driver: reason %d, %d nodes of %d\n", s, hs[s].reason,
                     hs[s].n_nodes, pl.ps[s].node_cap); continue; }
             o_.n_cells = hs[s].n_cells;
             if (p.dig_on && J.sets[s].n_reads > 0) cigar_digest_set(J.sets[s].seqs[0], J.sets[s].lens[0], hs[s].cigar_dig);
@@ -603,37 +603,31 @@ void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::
     });
     dbg.msa_check(hs, out);
     dbg.consensus_check(hs, out);
-    // (a set with a node out of edge slots gains nothing from a pass with more node slots: -(s + 1) tells the caller to take it to the last pass -- `roomy`
-    //  above -- at once, and to the host driver if that was this one: a terminal with more than POA_TERM_MAX edges)
-    for (int s = 0; s < J.n_sets; ++s) if (need_fb[s]) fallback->push_back(need_fb[s] == 2 ? -(s + 1) : s);
-    if (fallback_reason) {
-        fallback_reason->clear();
-        for (int s = 0; s < J.n_sets; ++s) if (need_fb[s]) { const int r = hs[s].pad;
-                fallback_reason->push_back(r >= 1000 ? (r - 1000 == ABPOA_HIP_STATUS_OVERFLOW ? 9 : 10) : (r >= 1 && r <= 8 ? r : 0)); }
-    }
+    // (a set with a node out of edge slots gains nothing from a pass with more node slots: the caller takes it to the last pass -- `roomy` above -- at once,
+    //  and to the host driver if that was this one: a terminal with more than POA_TERM_MAX edges)
+    for (int s = 0; s < J.n_sets; ++s) if (need_fb[s]) fallback->push_back({s, host_reason_of(hs[s].reason), hs[s].reason == POA_WHY_EDGE_SLOTS});
 }
 
 // ---- stage 11: ABPOA_HIP_VERBOSE: why sets left the pass
-void report_fallbacks(const Job &J, const std::vector<int> *fallback) {
+void report_fallbacks(const Job &J, const std::vector<SetFallback> &fallback) {
     const PoaState *hs = (const PoaState *)(J.C->graph.host + J.L.o_state);
-    if (!opt_set("ABPOA_HIP_VERBOSE") || fallback->empty()) return;
-    int hist[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int n_slots = 0;
-    int dp_arena = 0, dp_scores = 0, dp_other = 0;      // DP status: arena too small for the rows' bands / direction words could not decide / anything else
-    for (int f : *fallback) {
-        const int s = f < 0 ? -f - 1 : f; const int r = hs[s].pad;
-        if (r == 5) { n_slots++; continue; }
-        if (r >= 1000) { if (r - 1000 == ABPOA_HIP_STATUS_OVERFLOW) dp_arena++; else if (r - 1000 == ABPOA_HIP_STATUS_NEED_SCORES) dp_scores++;
-                else dp_other++; }
-        hist[r >= 1000 ? 5 : (r >= 0 && r < 5 ? r : (r == 6 ? 7 : 6))]++;
-        if (!(r >= 1000 || (r >= 0 && r < 7))) fprintf(stderr,
-                "[abpoa-hip]   set %d: reason code %d (7: row order walk, 8: MSA rank walk, 1000 + a negative DP status: " "%d)\n", s, r, r - 1000);
+    if (!opt_set("ABPOA_HIP_VERBOSE") || fallback.empty()) return;
+    int n[MSA_HOST_REASONS] = {0};
+    int dp_scores = 0;      // DP status: direction words could not decide (the arena too small for the rows' bands has a host reason of its own)
+    for (const SetFallback &f : fallback) {
+        const int r = hs[f.set].reason;
+        n[f.why]++;
+        if (r - POA_WHY_DP_STATUS == ABPOA_HIP_STATUS_NEED_SCORES) dp_scores++;
+        if (f.why == HOST_WHY_ORDER_WALK || f.why == HOST_WHY_RANK_WALK || (f.why == HOST_WHY_OTHER && r != POA_WHY_NONE)) fprintf(stderr,
+                "[abpoa-hip]   set %d: reason code %d (7: row order walk, 8: MSA rank walk, 1000 + a negative DP status: " "%d)\n", f.set, r, r - 1000);
     }
-    if (hist[5]) fprintf(stderr, "[abpoa-hip]   DP status: arena too small for the bands %d, direction words undecided %d, other %d\n", dp_arena,
-            dp_scores, dp_other);
+    const int n_dp = n[HOST_WHY_DP_ARENA] + n[HOST_WHY_DP_OTHER];
+    if (n_dp) fprintf(stderr, "[abpoa-hip]   DP status: arena too small for the bands %d, direction words undecided %d, other %d\n", n[HOST_WHY_DP_ARENA],
+            dp_scores, n[HOST_WHY_DP_OTHER] - dp_scores);
     fprintf(stderr, "[abpoa-hip] fallback reasons: node cap at init %d, pred CSR cap %d, cigar cap %d, node slots in the fuse "
             "phase %d, edge slots of a node full (redone in the last pass) %d, DP status %d, projected node growth "
-            "(early exit at read 10) %d, other %d\n", hist[1], hist[2], hist[3], hist[4], n_slots, hist[5], hist[7], hist[6] + hist[0]);
+            "(early exit at read 10) %d, other %d\n", n[HOST_WHY_NODES_AT_INIT], n[HOST_WHY_PRED_SLOTS], n[HOST_WHY_CIGAR_SLOTS], n[HOST_WHY_NODES_IN_FUSE],
+            n[HOST_WHY_EDGE_SLOTS], n_dp, n[HOST_WHY_GROWTH], n[HOST_WHY_OTHER] + n[HOST_WHY_ORDER_WALK] + n[HOST_WHY_RANK_WALK]);
 }
 
 void finish_stats(const Job &J, const std::vector<char> &need_fb, DeviceRunStats *stats) {
@@ -650,8 +644,8 @@ void finish_stats(const Job &J, const std::vector<char> &need_fb, DeviceRunStats
 // force_general: every alignment through the general kernel; *want_general: the final LDS plan has no fast row loop for this job although the first estimate had
 // one (ragged sets: one node factor more, wider rows -- the score width can flip to 32 bits): the caller runs the job again with force_general
 static int run_msa_device_body(const abpoa_hip_scoring_t *sc_in, int n_sets, const abpoa_hip_readset_t *sets, abpoa_hip_msa_t *out, int n_threads,
-                               std::vector<int> *fallback, DeviceRunStats *stats, double node_factor, unsigned flags, int device, int slot, bool force_general, bool *want_general,
-                               std::vector<int> *fallback_reason) {
+                               const DevicePass &pass, std::vector<SetFallback> *fallback, DeviceRunStats *stats, bool force_general, bool *want_general) {
+    const int slot = pass.slot; int device = pass.device;
     if (slot < 0 || slot >= MSA_DEVICE_SLOTS) { set_err("bad device slot %d", slot); return ABPOA_HIP_EINVAL; }
     std::lock_guard<std::mutex> lk(g_cache_mu[slot]);
     if (device < 0) device = engine_device();
@@ -662,7 +656,7 @@ static int run_msa_device_body(const abpoa_hip_scoring_t *sc_in, int n_sets, con
     fallback->clear();
     if (stats) memset(stats, 0, sizeof(*stats));
     J.t_begin = now_s();
-    J.pl = plan_device_job(sc_in, n_sets, sets, node_factor, flags, force_general);
+    J.pl = plan_device_job(sc_in, n_sets, sets, pass.node_factor, pass.flags, force_general);
     J.any_w = false; for (int s = 0; s < n_sets && !J.any_w; ++s) J.any_w = sets[s].weights != nullptr;
     lay_out(J.pl, n_sets, J.any_w, J.L, &J.dl_bytes);
     if ((rc = fit_device(J)) || (rc = upload_reads(J))) return rc;
@@ -673,20 +667,20 @@ static int run_msa_device_body(const abpoa_hip_scoring_t *sc_in, int n_sets, con
     if ((rc = queue_job(J, dbg))) return rc;
     fill_stats(J, stats);
     std::vector<char> need_fb;
-    collect_results(J, dbg, out, need_fb, fallback, fallback_reason);
-    report_fallbacks(J, fallback);
+    collect_results(J, dbg, out, need_fb, fallback);
+    report_fallbacks(J, *fallback);
     if (stats) finish_stats(J, need_fb, stats);
     return ABPOA_HIP_OK;
 }
 
-int run_msa_device(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, abpoa_hip_msa_t *out, int n_threads,
-                   std::vector<int> *fallback, DeviceRunStats *stats, double node_factor, unsigned flags, int device, int slot, std::vector<int> *fallback_reason) {
+int run_msa_device(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, abpoa_hip_msa_t *out, int n_threads, const DevicePass &pass,
+                   std::vector<SetFallback> *fallback, DeviceRunStats *stats) {
     bool want_general = false;
-    const int rc = run_msa_device_body(sc, n_sets, sets, out, n_threads, fallback, stats, node_factor, flags, device, slot, false, &want_general, fallback_reason);
+    const int rc = run_msa_device_body(sc, n_sets, sets, out, n_threads, pass, fallback, stats, false, &want_general);
     if (rc != ABPOA_HIP_EINVAL || !want_general) return rc;
     // the job stays on the device: the general kernel takes what the fast row loops' final plan could not (it used to leave for the host driver)
     want_general = false;
-    return run_msa_device_body(sc, n_sets, sets, out, n_threads, fallback, stats, node_factor, flags, device, slot, true, &want_general, fallback_reason);
+    return run_msa_device_body(sc, n_sets, sets, out, n_threads, pass, fallback, stats, true, &want_general);
 }
 
 }  // namespace abpoa_hip

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <vector>
 #include "../../include/abpoa_hip.h"
+#include "device_codes.h"
 
 namespace abpoa_hip {
 
@@ -25,7 +26,7 @@ struct DeviceRunStats {
 bool msa_device_eligible(const abpoa_hip_scoring_t *sc, unsigned flags);
 // A read-set whose reads differ much in length (more than an eighth of the longest, at least 64 bases): its band sits that far from the alignment's path in every
 // row (reference abpoa_align.h:34-35), so its rows are wider than 2 w by the difference -- run_msa_device gives it `band_extra` columns and the wide row loop.
-// A job that has such sets cannot take the all-rounds kernel: abpoa_hip_msa_batch runs them as a batch of their own (msa_hip.cpp deal_batches).
+// A job that has such sets cannot take the all-rounds kernel: abpoa_hip_msa_batch runs them as a batch of their own (msa_passes.cpp deal_batches).
 inline bool msa_device_set_is_ragged(const abpoa_hip_readset_t &S) {
     if (S.n_reads < 2) return false;
     int mx = 0, mn = 0x7fffffff;
@@ -34,12 +35,26 @@ inline bool msa_device_set_is_ragged(const abpoa_hip_readset_t &S) {
     return mx - mn > tol;
 }
 
-// Consensus of every set in out[]; sets whose graph outgrew a device capacity are listed in `fallback` (out[] zeroed for
-// them) and must be redone (with a larger node_factor, or by the host driver; an entry -(s + 1) is set s with a node out of edge slots: more node slots
-// would not help, the last pass does).  node_factor: node slots per set = factor x
-// longest read; 4096 and more: the last pass -- every node also has an edge slot per read (score records instead of direction words).  ABPOA_HIP_ENOMEM: the job does not fit the device (split it); EINVAL: not a job for the device driver.
-// device < 0: the device the engine was initialised on.  slot: which of the per-worker pool caches to use (one worker = one device queue of
-// the multi-GPU batch call; workers may share a device); a slot runs one job at a time.
+// Why a read-set goes to the host driver, as abpoa_hip_get_host_reasons counts them (abpoa_amd/api.py HOST_REASONS names the same slots)
+enum HostReason : int32_t {
+    HOST_WHY_OTHER = 0, HOST_WHY_NODES_AT_INIT = 1, HOST_WHY_PRED_SLOTS = 2, HOST_WHY_CIGAR_SLOTS = 3, HOST_WHY_NODES_IN_FUSE = 4, HOST_WHY_EDGE_SLOTS = 5,
+    HOST_WHY_GROWTH = 6, HOST_WHY_ORDER_WALK = 7, HOST_WHY_RANK_WALK = 8, HOST_WHY_DP_ARENA = 9, HOST_WHY_DP_OTHER = 10,
+    HOST_WHY_JOB = 11,            // the job's options are the host driver's / the set's pass did not fit the device
+};
+constexpr int MSA_HOST_REASONS = HOST_WHY_JOB + 1;
+// the one mapping from what a kernel left in PoaState.reason (device_codes.h)
+inline HostReason host_reason_of(int device_reason) {
+    if (device_reason >= POA_WHY_DP_STATUS) return device_reason - POA_WHY_DP_STATUS == ABPOA_HIP_STATUS_OVERFLOW ? HOST_WHY_DP_ARENA : HOST_WHY_DP_OTHER;
+    return device_reason >= POA_WHY_NODES_AT_INIT && device_reason <= POA_WHY_RANK_WALK ? (HostReason)device_reason : HOST_WHY_OTHER;
+}
+// A set that left a pass of run_msa_device (out[] zeroed for it): it must be redone, with a larger node factor or by the host driver.  edge_slots: a node ran
+// out of edge slots -- more node slots would not help, the last pass does.
+struct SetFallback { int set; HostReason why; bool edge_slots; };
+// One pass on one device queue.  node_factor: node slots per set = factor x longest read; 4096 and more: the last pass -- every node also has an edge slot per
+// read (score records instead of direction words).  device < 0: the device the engine was initialised on.  slot: which of the per-worker pool caches to use
+// (one worker = one device queue of the multi-GPU batch call; workers may share a device); a slot runs one job at a time.
+struct DevicePass { double node_factor; unsigned flags; int device = -1, slot = 0; };
+
 constexpr int MSA_DEVICE_SLOTS = 16;
 // Wide-band jobs (10 kb reads: one wavefront per alignment, tens of KB of LDS each): how many read-sets the device holds at once -- workgroups per CU by
 // the wide row loop's LDS x CUs.  A launch with more alignments than that runs its workgroups in turns, and because the alignments of a round take
@@ -47,12 +62,9 @@ constexpr int MSA_DEVICE_SLOTS = 16;
 int msa_device_resident_sets(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets);
 // frees every cached pool of every device queue (abpoa_hip_trim)
 void release_msa_device_caches();
-int run_msa_device(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, abpoa_hip_msa_t *out, int n_threads,
-                   std::vector<int> *fallback, DeviceRunStats *stats, double node_factor, unsigned flags, int device = -1, int slot = 0,
-                   std::vector<int> *fallback_reason = nullptr);
-// fallback_reason (optional, parallel to fallback): why the set left the pass -- 1 node slots at the first read, 2 predecessor list slots, 3 cigar slots,
-// 4 node slots in the fuse phase, 5 edge / aligned slots of a node, 6 projected node growth, 7 row-order walk, 8 MSA rank walk, 9 DP arena too small for the
-// bands, 10 other DP status, 0 other (abpoa_hip_get_host_reasons)
-constexpr int MSA_HOST_REASONS = 12;
+// Consensus / MSA of every set in out[]; the sets whose graph outgrew a device capacity are listed in `fallback`, in set order.
+// ABPOA_HIP_ENOMEM: the job does not fit the device (split it); EINVAL: not a job for the device driver.
+int run_msa_device(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, abpoa_hip_msa_t *out, int n_threads, const DevicePass &pass,
+                   std::vector<SetFallback> *fallback, DeviceRunStats *stats);
 
 }  // namespace abpoa_hip

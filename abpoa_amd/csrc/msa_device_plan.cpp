@@ -191,7 +191,7 @@ void choose_kernels(DevicePlan &P, int n_sets, const abpoa_hip_readset_t *sets, 
         if (P.general) P.fast_local = false;
     }
     // direction-plane arenas (dir_plane.h) whenever the penalties allow it: 2 / 4 bytes per cell instead of 8 - 32; ABPOA_HIP_NODIR=1 keeps the score records
-    // the last pass of the ladder (msa_hip.cpp device_passes): edge slots for one edge per read at every node -- a node takes at most one new in-edge and one new
+    // the last pass of the ladder (msa_passes.cpp run_pass_ladder): edge slots for one edge per read at every node -- a node takes at most one new in-edge and one new
     // out-edge per read, so a set can no longer run out of them (the terminals keep their pools: reads that start / end on different nodes); score records
     // instead of direction words there (dir_plane.h names a predecessor by its list index in four bits)
     P.roomy = P.node_factor >= 4096.0;

@@ -99,7 +99,7 @@ __device__ __forceinline__ void poa_prepare_body(const PoaDev &p, const int s, c
             const float rem = bq > 1e-4f ? (a / bq) * __logf((1.f + (N + 0.5f) * bq) / (1.f + 10.5f * bq)) : (A > B ? A : B) * (N - 10.f);
             doomed = (float)n + 1.1f * rem > (float)S.node_cap;
         }
-        if (doomed && tid == 0) { st->status = POA_ST_FALLBACK; st->pad = 6; }
+        if (doomed && tid == 0) { st->status = POA_ST_FALLBACK; st->reason = POA_WHY_GROWTH; }
     }
     if (status != POA_ST_OK || doomed || k >= S.n_reads) {          // nothing to align for this set in this round: both DP kernels skip it
         if (tid == 0) { AlnDesc d; memset(&d, 0, sizeof(d)); d.n_rows = 3; d.bits = 16; d.flags = ALN_SKIP; p.aln[s] = d; p.out[s].status = 0; p.out[s].n_cigar = 0; p.out[s].n_cells = 0; }
@@ -111,8 +111,8 @@ __device__ __forceinline__ void poa_prepare_body(const PoaDev &p, const int s, c
     int32_t *remain = p.row_remain + N0;
     // (1) heaviest out-edge per row (first maximum wins, reference :262-268)
     extern __shared__ unsigned jump_lds[];                 // [n] remaining-length jump records (see (2)), when the launch provides them
-    const bool in_lds = p.pad > 0 && n <= p.pad;
-    uint8_t *np_lds = (uint8_t *)(jump_lds + p.pad);       // [n] in-degree per row (row 0: none), for (3)
+    const bool in_lds = p.lds_rows > 0 && n <= p.lds_rows;
+    uint8_t *np_lds = (uint8_t *)(jump_lds + p.lds_rows);       // [n] in-degree per row (row 0: none), for (3)
     {
         // four rows per thread and pass, every load level issued for all four before the next one: the chain order -> node -> edge
         // slots -> row of the successor is four dependent HBM/L2 round trips, and a thread owns ~10 rows (150 on a 10 kb graph)
@@ -296,7 +296,7 @@ __device__ __forceinline__ void poa_prepare_body(const PoaDev &p, const int s, c
         d.cigar_cap = S.cigar_cap; d.flags = (p.general & 1) ? 0 : ALN_FAST_OK; d.pad0 = S.band_extra;
         d.query_off = p.read_off[S.read0 + k]; d.row0 = N0; d.poff0 = N0; d.pred0 = S.pred0; d.out0 = S.pred0;
         d.plane_off = S.plane_off; d.plane_cap = S.plane_cap / (d.bits / 8); d.cigar_off = S.cigar_off;
-        if (overflow || n + qlen + 8 > S.cigar_cap) { st->status = POA_ST_FALLBACK; st->pad = overflow ? 2 : 3; d.flags = ALN_SKIP; d.n_rows = 3; }
+        if (overflow || n + qlen + 8 > S.cigar_cap) { st->status = POA_ST_FALLBACK; st->reason = overflow ? POA_WHY_PRED_SLOTS : POA_WHY_CIGAR_SLOTS; d.flags = ALN_SKIP; d.n_rows = 3; }
         p.aln[s] = d;
         p.out[s].status = 0; p.out[s].n_cigar = 0; p.out[s].n_cells = 0;
     }
@@ -312,7 +312,7 @@ __device__ __forceinline__ void poa_fuse_body(const PoaDev &p, const int s, cons
     PoaState *st = p.state + s;
     if (uni(st->status) != POA_ST_OK || k >= S.n_reads) return;
     AlnOut res = p.out[s]; res.status = uni(res.status); res.n_cigar = uni(res.n_cigar);
-    if (res.status != 0) { if (tid == 0) { st->status = POA_ST_FALLBACK; st->pad = 1000 + res.status; } return; }
+    if (res.status != 0) { if (tid == 0) { st->status = POA_ST_FALLBACK; st->reason = POA_WHY_DP_STATUS + res.status; } return; }
     const int64_t N0 = S.node0;
     const int n_old = uni(st->n_nodes), qlen = p.read_len[S.read0 + k], n_cigar = res.n_cigar;
     const bool rc_read = p.is_rc && uni((int)p.is_rc[S.read0 + k]) != 0;      // (-s: the reverse complement of this read won, reference :331-334)
@@ -343,7 +343,7 @@ __device__ __forceinline__ void poa_fuse_body(const PoaDev &p, const int s, cons
     __syncthreads();
     // F2: walk the query in chunks of 64 positions
     int n_nodes = n_old, prev_c = 0 /* source */, prev_new_c = 0, carry_ar = 0 /* row of the source */, carry_sq = -1;
-    bool fail = false, fail_slots = false;      // (fail_slots: an edge / aligned list is full -- more node slots would not help, PoaState.pad 5)
+    bool fail = false, fail_slots = false;      // (fail_slots: an edge / aligned list is full -- more node slots would not help, POA_WHY_EDGE_SLOTS)
     // adds edge from -> to (both lane-private; `from_new` / `to_new`: the node was created by this read, its lists are still empty
     // apart from what this very walk put there, which is known without a load)
     // per-base weights of this read (-Q), reference :634-667: an edge takes the weight of the base it leads to
@@ -457,9 +457,9 @@ __device__ __forceinline__ void poa_fuse_body(const PoaDev &p, const int s, cons
     bool any_fail = __syncthreads_or(fail);
     if (!any_fail) { add_edge(tid == 0, prev_c, prev_new_c != 0, 1, false, wq ? wq[qlen - 1] : 1); any_fail = __syncthreads_or(fail); }      // reference :667: the last base's weight
     const bool any_slots = __syncthreads_or(fail_slots);
-    if (tid == 0) { sh_fail = any_fail ? (any_slots ? 5 : 4) : 0; sh_nodes = n_nodes; }
+    if (tid == 0) { sh_fail = any_fail ? (any_slots ? POA_WHY_EDGE_SLOTS : POA_WHY_NODES_IN_FUSE) : POA_WHY_NONE; sh_nodes = n_nodes; }
     __syncthreads();
-    if (sh_fail) { if (tid == 0) { st->status = POA_ST_FALLBACK; st->pad = sh_fail; } return; }
+    if (sh_fail) { if (tid == 0) { st->status = POA_ST_FALLBACK; st->reason = sh_fail; } return; }
     n_nodes = sh_nodes;
     // F4: new row order = old order with every run of new nodes spliced in after its anchor
     int carry = 0;

@@ -39,7 +39,7 @@ struct PoaSet {                    // immutable per read-set
 };
 
 struct PoaState {                  // mutable per read-set
-    int32_t n_nodes, status, order_buf, pad;     // order_buf: which row_node buffer is current; pad: fall-back reason
+    int32_t n_nodes, status, order_buf, reason;  // order_buf: which row_node buffer is current; reason: why the set fell back (device_codes.h POA_WHY_*)
     int32_t cons_len, msa_len;     // heaviest-bundling consensus length (poa_consensus_kernel); MSA columns (poa_msa_rank_kernel)
     int32_t grow_n2, grow_n6;      // nodes after 2 / 6 reads: the growth model of the doomed-pass test (poa_bodies.h)
     int64_t n_cells;               // DP cells over all alignments so far
@@ -62,7 +62,7 @@ struct PoaDev {                    // everything the poa_* kernels need; passed 
     int32_t n_sets, m;
     int32_t max_mat, min_mis, o1, e1, o2, e2, wb; float wf;
     int32_t gap_mode, round;       // round k: read k of every set is aligned / fused
-    int32_t max_qlen, pad;         // pad: node capacity of the prepare kernel's LDS jump records (4 bytes each; 0 = use the global-memory sweep)
+    int32_t max_qlen, lds_rows;    // lds_rows: node capacity of the prepare kernel's LDS jump records (4 bytes each; 0 = use the global-memory sweep)
     int32_t aln_cap;               // slots per node in nd_aln (m - 1)
     int32_t rid_words;             // read-id bitsets per out-edge (abpoa_para_t.use_read_ids: MSA output): 64-bit words per edge, 0 = not kept
     int32_t order_mode;            // 0: the row order is maintained incrementally by the fuse phase (global mode: any topological order gives the same result);

@@ -28,13 +28,13 @@ __global__ void __launch_bounds__(64) poa_init_kernel(const PoaDev p) {
     if (s >= p.n_sets) return;
     const PoaSet S = p.sets[s];
     PoaState *st = p.state + s;
-    if (lane == 0) { st->order_buf = 0; st->n_cells = 0; st->algo_bytes = 0; st->pad = 0; st->cons_len = 0; st->msa_len = 0; st->cigar_dig = 0; for (int i = 0; i < 4; ++i) st->t_phase[i] = 0;
+    if (lane == 0) { st->order_buf = 0; st->n_cells = 0; st->algo_bytes = 0; st->reason = POA_WHY_NONE; st->cons_len = 0; st->msa_len = 0; st->cigar_dig = 0; for (int i = 0; i < 4; ++i) st->t_phase[i] = 0;
             st->algo_bytes_before = 0; }
     if (S.n_reads <= 0) { if (lane == 0) { st->n_nodes = 2; st->status = POA_ST_OK; } return; }
     const int L = p.read_len[S.read0];
     const uint8_t *seq = p.reads + p.read_off[S.read0];
     const int n = L + 2;
-    if (n > S.node_cap) { if (lane == 0) { st->n_nodes = 2; st->status = POA_ST_FALLBACK; st->pad = 1; } return; }
+    if (n > S.node_cap) { if (lane == 0) { st->n_nodes = 2; st->status = POA_ST_FALLBACK; st->reason = POA_WHY_NODES_AT_INIT; } return; }
     const int64_t N0 = S.node0;
     for (int u = lane; u < n; u += 64) {
         // node ids: 0 = source, 1 = sink, 2 + i = base i of the read
@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(64) poa_consensus_kernel(const PoaDev p) {
         }
         __syncthreads();
     }
-    if (lane == 0) { st->cons_len = len; if (overflow) { st->status = POA_ST_FALLBACK; st->pad = 5; } }
+    if (lane == 0) { st->cons_len = len; if (overflow) { st->status = POA_ST_FALLBACK; st->reason = POA_WHY_EDGE_SLOTS; } }      // (a full consensus pool has always reported this code)
 }
 
 
@@ -500,7 +500,7 @@ __global__ void __launch_bounds__(64) poa_order_kernel(const PoaDev p) {
     const bool ok = done >= 0 ? done == 1 : (n <= p.order_lds ? poa_order_body<true>(p, S, n, order) : poa_order_body<false>(p, S, n, order));
     // (the sink is the last node the walk reaches, reference :203-206; anything else means the graph is not what the fuse phase should have left)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (threadIdx.x == 0 && (!ok || ld_fresh(order + n - 1) != 1)) { st->status = POA_ST_FALLBACK; st->pad = 7; }
+    if (threadIdx.x == 0 && (!ok || ld_fresh(order + n - 1) != 1)) { st->status = POA_ST_FALLBACK; st->reason = POA_WHY_ORDER_WALK; }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -570,7 +570,7 @@ __global__ void __launch_bounds__(64) poa_msa_rank_kernel(const PoaDev p) {
     const int n = uni(st->n_nodes);
     if (n <= 2) { if (threadIdx.x == 0) st->msa_len = 0; return; }
     const int len = 4 * n <= 2 * p.order_lds ? poa_msa_rank_body<true>(p, S, n) : poa_msa_rank_body<false>(p, S, n);      // (four tables in the space of the order kernel's two)
-    if (threadIdx.x == 0) { if (len < 0) { st->status = POA_ST_FALLBACK; st->pad = 8; st->msa_len = 0; } else st->msa_len = len; }
+    if (threadIdx.x == 0) { if (len < 0) { st->status = POA_ST_FALLBACK; st->reason = POA_WHY_RANK_WALK; st->msa_len = 0; } else st->msa_len = len; }
 }
 
 // MSA output, pass 2 (after the host has laid the sets' results out back to back: msa_off): rows of gap codes, then every node writes its base into the
@@ -606,7 +606,7 @@ static hipError_t launch_k(void (*kern)(const PoaDev), const PoaDev &p, hipStrea
 hipError_t launch_poa_init(const PoaDev &p, hipStream_t s) { return launch_k(poa_init_kernel, p, s); }
 hipError_t launch_poa_prepare(const PoaDev &p, hipStream_t s) {
     if (p.n_sets <= 0) return hipSuccess;
-    hipLaunchKernelGGL(poa_prepare_kernel, dim3(p.n_sets), dim3(GT), (size_t)5 * (size_t)(p.pad > 0 ? p.pad : 0), s, p);      // p.pad: rows the LDS records hold (4 + 1 bytes each; 0: none)
+    hipLaunchKernelGGL(poa_prepare_kernel, dim3(p.n_sets), dim3(GT), (size_t)5 * (size_t)(p.lds_rows > 0 ? p.lds_rows : 0), s, p);      // p.lds_rows: rows the LDS records hold (4 + 1 bytes each; 0: none)
     return hipGetLastError();
 }
 hipError_t launch_poa_fuse(const PoaDev &p, hipStream_t s) {

@@ -3,7 +3,7 @@
 Read-sets share nothing, so a rank (or a device queue inside one process) owns a contiguous slice of the set indices and there is
 no data-path collective.  `deal_by_cost` is the in-process dealer of the multi-device batch call: sets sorted by estimated cost
 (sum of read lengths x reads, the DP's row x band product) and dealt round-robin, heaviest first, so every device queue gets the same
-mix of long and short jobs; the library's own C++ dealer (msa_hip.cpp) follows the same rule."""
+mix of long and short jobs; the library's own C++ dealer (msa_passes.cpp) follows the same rule."""
 
 
 def shard_range(total, world, rank):

@@ -481,7 +481,7 @@ def test_rows_wider_than_the_band_estimate_stay_on_the_device(engine):
 
 def test_ragged_sets_of_a_mixed_job_run_as_a_batch_of_their_own(engine, monkeypatch):
     """A banded global job of uniform read-sets with two ragged ones among them: abpoa_hip_msa_batch hands the ragged sets to the device passes as a batch of
-    their own (msa_hip.cpp split_ragged), so the uniform ones keep the all-rounds kernel; results in caller order, equal to the oracle-backed run's and to the
+    their own (msa_passes.cpp split_ragged), so the uniform ones keep the all-rounds kernel; results in caller order, equal to the oracle-backed run's and to the
     one-batch form (ABPOA_HIP_NO_RAGGED_SPLIT=1: lock-step launches for everything, no all-rounds launch)."""
     import numpy as np
     import helpers as H
