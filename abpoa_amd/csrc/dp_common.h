@@ -303,12 +303,11 @@ __device__ __forceinline__ bool takes_fast(const DevBatch &b, const AlnDesc &d) 
            d.qlen <= b.lds.q_cap && !(b.dbg & 64);
 }
 
-// ... and among those, the ones whose rows are wide enough for NW wavefronts per alignment (dp_wide_rows.hip); the rest keep one wavefront
+// ... and among those, the ones whose rows are wide enough for the wide row loop (dp_wide_rows.hip); the rest take the narrow one
 // (AlnDesc.pad0: columns the rows are expected to be wider than 2 w -- the device-resident driver sets it for read-sets whose reads differ much in length;
 //  half of it counts as band half-width for the choice of the row loop, nothing else reads it)
 __device__ __forceinline__ bool takes_wide(const DevBatch &b, const AlnDesc &d) {
-    const int weff = d.w + (d.pad0 >> 1);
-    return b.lds.wide_nw >= 1 && weff >= b.lds.wide_w_lo && weff <= b.lds.wide_w_hi;
+    return takes_wide_band(b.lds, d.w + (d.pad0 >> 1));
 }
 
 // ... and which of the fast alignments write direction words instead of score records (dir_plane.h): dir_mode 1 = the narrow-band ones of the launch,
@@ -331,7 +330,6 @@ static hipError_t launch_one(K kern, const DevBatch &b, hipStream_t stream, int 
 // per-TU launchers (one translation unit per kernel family: parallel builds, one row loop per file)
 hipError_t launch_fast_rows(const DevBatch &b, hipStream_t stream);       // dp_fast_rows.hip
 hipError_t launch_wide_rows(const DevBatch &b, hipStream_t stream);       // dp_wide_rows.hip
-hipError_t launch_team_rows(const DevBatch &b, hipStream_t stream);       // dp_team_rows.hip
 hipError_t launch_local_rows(const DevBatch &b, hipStream_t stream);      // dp_local_rows.hip
 hipError_t launch_fast_tail(const DevBatch &b, hipStream_t stream);       // dp_fast_tail.hip
 hipError_t launch_general(const DevBatch &b, hipStream_t stream);         // dp_general.hip

@@ -218,11 +218,10 @@ int BatchStream::run() {
             make_lds_plan(sc, max_qlen, max_bits, est_cols, (int)pass.size(), &b.lds);
             for (const AlnDesc &d : pass) b.bits_mask |= d.bits == 16 ? 1 : 2;
             bool any_wide = false, all_wide = true;
-            for (const AlnDesc &d : pass) { const bool wd = d.w >= b.lds.wide_w_lo && d.w <= b.lds.wide_w_hi; any_wide |= wd; all_wide &= wd; }
-            if (!any_wide) b.lds.wide_nw = 0;
-            b.lds.narrow_off = (b.lds.wide_nw >= 1 && all_wide) ? 1 : 0;
+            for (const AlnDesc &d : pass) { const bool wd = takes_wide_band(b.lds, d.w); any_wide |= wd; all_wide &= wd; }
+            if (!any_wide) b.lds.wide_on = 0;
+            b.lds.narrow_off = (b.lds.wide_on >= 1 && all_wide) ? 1 : 0;
         }
-        if (b.lds.wide_nw > 1) dir = false;
         // (ABPOA_HIP_DIR_WIDE=1: words for the wide-band alignments too -- the device-resident driver does that by itself when the record arenas of a
         //  job do not fit the device; here it is a test switch)
         const bool dir_wide = dir && opt_int("ABPOA_HIP_DIR_WIDE", 0) > 0;
@@ -235,7 +234,7 @@ int BatchStream::run() {
             const bool fast_a = (d.flags & ALN_FAST_OK) && fast_global_job(sc->gap_mode, sc->align_mode, sc->wb, sc->gap_ext1) && fast_global_aln(sc->gap_mode, d.w, d.pad0) &&
                                 b.lds.fr_cols > 0 &&
                                 d.qlen <= b.lds.q_cap && !(dbg_ & 64);
-            const bool dir_a = dir && fast_a && (dir_wide || !(b.lds.wide_nw >= 1 && d.w >= b.lds.wide_w_lo && d.w <= b.lds.wide_w_hi));
+            const bool dir_a = dir && fast_a && (dir_wide || !takes_wide_band(b.lds, d.w));
             d.plane_cap = dir_a ? (first_pass ? dir_est_cells_[todo[t]] : dir_full_cells_[todo[t]]) : (first_pass ? est_cells_[todo[t]] : full_cells_[todo[t]]);
             d.plane_off = plane_bytes; plane_bytes += (int64_t)align_up((size_t)d.plane_cap * (d.bits / 8) + 64 * 8 * 4);   // + 64 records of slack (fast loop stores whole 64-lane chunks)
             pass[t] = d;
@@ -419,12 +418,12 @@ void abpoa_hip_shutdown(void) {
 const char *abpoa_hip_last_error(void) { std::lock_guard<std::mutex> lk(g_err_mu); memcpy(g_err_copy, g_err, sizeof(g_err)); return g_err_copy; }
 void abpoa_hip_get_stats(abpoa_hip_stats_t *out) { std::lock_guard<std::mutex> lk(g.stats_mu); *out = g.stats; }
 void abpoa_hip__dir_counts(long long *out) { out[0] = __atomic_exchange_n(&g_dir_counts[0], 0, __ATOMIC_RELAXED); out[1] = __atomic_exchange_n(&g_dir_counts[1], 0, __ATOMIC_RELAXED); }
-// (test hook, host only: the LDS carve-up of the wide row loop for a launch of n_aln alignments -- out: wide_nw, ring rows, LDS bytes per workgroup,
+// (test hook, host only: the LDS carve-up of the wide row loop for a launch of n_aln alignments -- out: wide_on, ring rows, LDS bytes per workgroup,
 //  workgroups per CU by the 1280-byte allocation granule of gfx950, the wide kernels' phase offset, the band half-widths [lo, hi] that take it)
 void abpoa_hip__wide_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max_bits, int n_aln, int *out) {
     abpoa_hip::LdsPlan L; const int pn = max_bits == 16 ? 16 : 8; const int w = sc->wb + (int)(sc->wf * (float)max_qlen);
     abpoa_hip::make_lds_plan(sc, max_qlen, max_bits, abpoa_hip::band_cols(abpoa_hip::padded_width(max_qlen, pn), w, pn, true), n_aln, &L);
-    out[0] = L.wide_nw; out[1] = L.wfr_rows; out[2] = L.total_wide; out[3] = L.total_wide > 0 ? abpoa_hip::wide_workgroups_per_cu(L.total_wide) : 0;
+    out[0] = L.wide_on; out[1] = L.wfr_rows; out[2] = L.total_wide; out[3] = L.total_wide > 0 ? abpoa_hip::wide_workgroups_per_cu(L.total_wide) : 0;
     out[4] = L.w_phase_off; out[5] = L.wide_w_lo; out[6] = L.wide_w_hi;
 }
 void abpoa_hip__debug_clocks(long long *out) { for (int i = 0; i < 10; ++i) { out[i] = g_dbg[i]; g_dbg[i] = 0; } }

@@ -65,13 +65,13 @@ struct LdsPlan {
     int32_t bt_wc;                // column-slice windows of the backtrack: columns per slice (0: the kernel's default)
     // --- fast row loop (dp_kernel.hip rows_fast): packed H|E score ring [fr_rows][words][fr_cols + 4] dwords at phase_off + fr_off
     int32_t fr_off, fr_rows, fr_cols;   // fr_rows: power of two <= 64; fr_cols: multiple of 64, 0 = fast loop disabled
-    // --- wide row loop (NW wavefronts per alignment, rows_fast<.., NW>): its own score ring [wfr_rows][words][wfr_cols + 4] at phase_off + fr_off,
-    //     then the exchange slots (wx_off, relative to phase_off); wide_nw = 0: not used by this launch
-    int32_t wfr_rows, wfr_cols, wx_off, wide_nw;
-    int32_t wide_w_lo, wide_w_hi; // an alignment takes the wide loop iff wide_w_lo <= its band half-width w <= wide_w_hi
+    // --- wide row loop (one wavefront per alignment, rows_fast<.., WIDEB>): its own score ring [wfr_rows][words][wfr_cols + 4] at w_phase_off + fr_off;
+    //     wx_off: end of that ring (relative to w_phase_off); wide_on = 0: not used by this launch
+    int32_t wfr_rows, wfr_cols, wx_off, wide_on;
+    int32_t wide_w_lo, wide_w_hi; // an alignment takes the wide loop iff wide_w_lo <= its band half-width w <= wide_w_hi (takes_wide_band below)
     int32_t narrow_off;           // 1: every alignment of the launch takes the wide loop -- the narrow row-loop kernels are not launched
     int32_t total_wide;           // dynamic LDS bytes of the wide row-loop kernel
-    // (the wide kernels' own carve-up: query at q_off packed two 4-bit codes to a byte, then the extended matrix at w_mx_off, then -- w_phase_off -- ring and exchange slots)
+    // (the wide kernels' own carve-up: query at q_off packed two 4-bit codes to a byte, then the extended matrix at w_mx_off, then -- w_phase_off -- the ring)
     int32_t w_mx_off, w_phase_off;
     // --- local row loop (rows_local.h): ring [loc_rows][words][loc_cols + 4] at phase_off + fr_off; loc_cols = 0: not used by this launch
     int32_t loc_rows, loc_cols, total_local;
@@ -134,6 +134,8 @@ __host__ __device__ inline bool fast_global_job(int gap_mode, int align_mode, in
     return align_mode == ABPOA_HIP_GLOBAL_MODE || align_mode == ABPOA_HIP_EXTEND_MODE;
 }
 __host__ __device__ inline bool fast_global_aln(int gap_mode, int w, int pad0) { return gap_mode != ABPOA_HIP_LINEAR_GAP || w + (pad0 >> 1) < LINEAR_FAST_W; }
+// ... and among those, the band half-widths (with half of a ragged set's extra columns: dp_common.h takes_wide) that take the wide row loop of the launch
+__host__ __device__ inline bool takes_wide_band(const LdsPlan &L, int w) { return L.wide_on >= 1 && w >= L.wide_w_lo && w <= L.wide_w_hi; }
 
 // Values per DP column in an arena of score records: one padded cell record of the fast loops (rows_fast.h FastFmt::CW) = the planes of the general kernel
 // (linear gaps: {H, match flag} in the fast loops, H alone in the general kernel)
@@ -143,7 +145,7 @@ inline int64_t padded_width(int qlen, int pn) { return (int64_t)((qlen + pn) / p
 inline int64_t band_cols(int64_t width, int w, int pn, bool banded) { const int64_t est = 2LL * w + 3 * pn + 32; return banded && est < width ? est : width; }
 // Direction words (dir_plane.h) instead of score records: what the penalties and the switches allow; each driver adds its own conditions
 inline bool dir_words_allowed(const abpoa_hip_scoring_t *sc) {
-    return dir_plane_usable(sc->gap_mode, sc->gap_open1, sc->gap_ext1, sc->gap_open2, sc->gap_ext2) && !opt_on("ABPOA_HIP_NODIR") && !(opt_int("ABPOA_HIP_TEAM", 0) > 1);
+    return dir_plane_usable(sc->gap_mode, sc->gap_open1, sc->gap_ext1, sc->gap_open2, sc->gap_ext2) && !opt_on("ABPOA_HIP_NODIR");
 }
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 

@@ -27,7 +27,6 @@ const Row kTable[] = {
     {"ABPOA_HIP_NOFAST", "T  1: no fast row loops (general kernel)"},
     {"ABPOA_HIP_NOWIDE", "T  1: no wide row loop"},
     {"ABPOA_HIP_NOXL", "T  1: no long-read form of the wide row loop"},
-    {"ABPOA_HIP_TEAM", "T  1 | 2 | 4 wavefronts per wide-band alignment"},
     {"ABPOA_HIP_LOCAL_TEAM", "T  1 / 0: the four-wavefront local row loop always / never"},
     {"ABPOA_HIP_WIDE_LO", "T  smallest band half-width that takes the wide loop [40]"},
     {"ABPOA_HIP_RING_ROWS", "T  depth of the wide loop's score ring (4 | 8 | 16)"},

@@ -320,7 +320,7 @@ void fill_poa_dev(Job &J) {
     p.cons_node = (int32_t *)(dg + L.o_cnode); p.cons_cov = (int32_t *)(dg + L.o_ccov); p.cons_base = dg + L.o_cbase;
 }
 
-// ---- the launch's LDS plan: sized for the widest rows expected, trimmed to the row-loop kernels that can have work (wide_nw, narrow_off), and the score
+// ---- the launch's LDS plan: sized for the widest rows expected, trimmed to the row-loop kernels that can have work (wide_on, narrow_off), and the score
 //      widths the rounds can meet
 int final_lds_plan(const Job &J, DevBatch &b) {
     const DevicePlan &pl = J.pl; const abpoa_hip_scoring_t *sc = &pl.sc;
@@ -334,10 +334,10 @@ int final_lds_plan(const Job &J, DevBatch &b) {
     // (a ring that wide does not fit -- int32 scores, convex gaps: the plain estimate then, and the ragged sets' rows that outgrow it are theirs alone)
     if (pl.max_extra > 0 && b.lds.fr_cols == 0) make_lds_plan(sc, pl.max_qlen, max_bits, est_plain, J.n_sets, &b.lds);
     // (no fast row loop takes anything: dp_common.h takes_fast / rows_local.h takes_local)
-    if (pl.general) { b.lds.wide_nw = 0; b.lds.fr_cols = 0; b.lds.loc_cols = 0; }
+    if (pl.general) { b.lds.wide_on = 0; b.lds.fr_cols = 0; b.lds.loc_cols = 0; }
     // the local row loop (rows_local.h takes_local): int16 scores, at most loc_cols columns, query codes in LDS; anything else is the general kernel's
     else if (pl.local) {
-        b.lds.wide_nw = 0;
+        b.lds.wide_on = 0;
         if (max_bits != 16 || b.lds.loc_cols <= 0 || (pl.max_qlen / 16 + 1) * 16 > b.lds.loc_cols || pl.max_qlen > b.lds.q_cap) {
                 set_err("local alignment outside the device row loop's range"); return ABPOA_HIP_EINVAL; }
     }
@@ -350,8 +350,8 @@ int final_lds_plan(const Job &J, DevBatch &b) {
     // (band half-widths as dp_common.h takes_wide counts them: with half of a ragged set's extra columns)
     const int w_min = std::min(sc->wb + (int)(sc->wf * (float)min_qlen), pl.max_extra ? pl.weff_lo : INT_MAX), w_top = std::max(pl.w_max, pl.weff_hi);
     const bool mixed = pl.max_extra > 0;      // (sets with and without extra columns: both loops may have work whatever the extremes say)
-    if (!mixed && (w_top < b.lds.wide_w_lo || w_min > b.lds.wide_w_hi)) b.lds.wide_nw = 0;                       // no read takes the wide loop
-    b.lds.narrow_off = (!mixed && b.lds.wide_nw >= 1 && w_min >= b.lds.wide_w_lo && w_top <= b.lds.wide_w_hi) ? 1 : 0;      // every read does
+    if (!mixed && (w_top < b.lds.wide_w_lo || w_min > b.lds.wide_w_hi)) b.lds.wide_on = 0;                       // no read takes the wide loop
+    b.lds.narrow_off = (!mixed && b.lds.wide_on >= 1 && w_min >= b.lds.wide_w_lo && w_top <= b.lds.wide_w_hi) ? 1 : 0;      // every read does
     return 0;
 }
 
@@ -369,7 +369,7 @@ int fill_dev_batch(Job &J, bool *want_general) {
     b.want_trace = 0; b.fresh_band = 1; b.want_lr = 0;
     b.dbg = opt_int("ABPOA_HIP_DBG", 0);      // (diagnostics: bit 7 keeps the row loop's counters in AlnOut.seg)
     b.mat = (const int32_t *)(di + L.o_mat); b.aln = p.aln; b.out = p.out;
-    b.dir_mode = (pl.dir && b.lds.wide_nw <= 1) ? (pl.dir_wide ? 2 : 1) : 0; b.row_sdist = p.row_sdist; b.row_pd = p.row_pd;
+    b.dir_mode = pl.dir ? (pl.dir_wide ? 2 : 1) : 0; b.row_sdist = p.row_sdist; b.row_pd = p.row_pd;
     b.query = p.reads; b.row_base = p.row_base; b.row_node_id = p.row_node_id; b.row_remain = p.row_remain; b.row_active = p.row_base;
     b.pred_off = p.pred_off; b.pred_row = p.pred_row; b.out_off = p.pred_off; b.out_row = p.pred_row;
     b.left = p.scratch; b.right = p.scratch;
@@ -396,7 +396,7 @@ void plan_rounds(Job &J) {
     const DevicePlan &pl = J.pl; const abpoa_hip_scoring_t *sc = &pl.sc; const PoaDev &p = J.p; const DevBatch &b = J.b; DevBatch &b_r = J.b_r;
     bool &dbg_sync = J.dbg_sync, &use_rounds = J.use_rounds; size_t &rounds_lds = J.rounds_lds;
     dbg_sync = opt_on("ABPOA_HIP_DEVSYNC");
-    use_rounds = !pl.local && pl.rounds_possible && !dbg_sync && b.lds.wide_nw == 0 && !(b.dbg & 64) && pl.max_reads > 2 && !opt_on("ABPOA_HIP_LOCKSTEP");
+    use_rounds = !pl.local && pl.rounds_possible && !dbg_sync && b.lds.wide_on == 0 && !(b.dbg & 64) && pl.max_reads > 2 && !opt_on("ABPOA_HIP_LOCKSTEP");
     b_r = b; rounds_lds = 0;
     if (use_rounds) {
         // (prepare: 5 bytes per row; fuse: 16 bytes per thread)

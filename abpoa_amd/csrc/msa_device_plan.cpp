@@ -10,12 +10,7 @@ namespace abpoa_hip {
 
 // LDS carve-up of one wavefront (engine.h LdsPlan) for a launch whose largest query is max_qlen, widest score type max_bits
 // and widest expected band est_cols columns.
-// (-DABPOA_HIP_WIDE_W3, experiment: three wavefronts per SIMD in the wide loop -- twelve workgroups per CU, ring depth down to 2)
-#ifdef ABPOA_HIP_WIDE_W3
-constexpr int WIDE_PER_CU_MAX = 12, WIDE_RING_MIN = 2;
-#else
 constexpr int WIDE_PER_CU_MAX = 8, WIDE_RING_MIN = 4;
-#endif
 void make_lds_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max_bits, int64_t est_cols, int n_aln, LdsPlan *Lp) {
     LdsPlan &L = *Lp;
     const int P = sc->gap_mode == ABPOA_HIP_LINEAR_GAP ? 1 : (sc->gap_mode == ABPOA_HIP_AFFINE_GAP ? 3 : 5);
@@ -68,50 +63,44 @@ void make_lds_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max_bits, in
     // wide row loop (dp_wide_rows.hip): alignments whose band half-width w is in [wide_w_lo, wide_w_hi] -- rows of 2..7 chunks of 64 columns --
     // go to the kernel that keeps every chunk of a row in registers; it has its own score ring (448 columns; depth by what fits:
     // predecessors up to 15 rows back are common in a graph of noisy reads).  ABPOA_HIP_NOWIDE=1 turns it off, ABPOA_HIP_RING_ROWS sets
-    // the depth, ABPOA_HIP_TEAM=1|2|4 sets the wavefronts per alignment.
-    L.wide_nw = 0; L.wfr_rows = L.wfr_cols = L.wx_off = L.total_wide = 0; L.wide_w_lo = 1; L.wide_w_hi = 0; L.narrow_off = 0; L.w_mx_off = L.w_phase_off = 0;
-    { const int mw_ = opt_int("ABPOA_HIP_TEAM", 0);
-      if (L.fr_cols && L.q_cap && !opt_on("ABPOA_HIP_NOWIDE")) {
-          // wavefronts per alignment: 1.  Teams of 2 / 4 (ABPOA_HIP_TEAM=2|4, dp_team_rows.hip) give identical results but are slower on gfx950
-          // as measured (3.9 k vs 3.1 k cycles per 5-chunk row): a row's ~370 instructions of scalar bookkeeping are repeated by every wavefront
-          // of the team and outweigh the ~28 instructions per chunk that the split saves (profiles/r2_team_vs_single.txt).
-          L.wide_nw = 1;
-          if (mw_ == 1 || mw_ == 2 || mw_ == 4) L.wide_nw = mw_;
-          // (rows wider than the 448-column ring -- reads of 20 kb and more: w = 10 + 0.01 L -- take the kernel's long-read form: 704 columns, 8 - 11 chunks a row)
-          L.wfr_cols = (est_cols > WIDE_RING_COLS && !opt_on("ABPOA_HIP_NOXL")) ? WIDE_RING_COLS_XL : WIDE_RING_COLS; L.wfr_rows = 16;
-          if (sc->m > 16) L.wide_nw = 0;      // (4-bit query codes)
-          L.w_mx_off = (int)align_up((size_t)(max_qlen + 2) / 2, 16); L.w_phase_off = L.w_mx_off + (int)align_up(4 * sc->m * (sc->m + 1), 16);
-          // ring words per column of the wide kernels: as the narrow loop's, but two instead of three for convex int32 (rows_fast.h EPACK: E as 16-bit
-          // differences to H, which needs gap-open + extend <= 65535)
-          const int fww = (P == 5 && max_bits == 32) ? 2 : fw;
-          if (P == 5 && (sc->gap_open1 + sc->gap_ext1 >= 65535 || sc->gap_open2 + sc->gap_ext2 >= 65535)) L.wide_nw = 0;      // (0xffff: "E is inf" in the compact spill records)
-          L.wide_w_lo = 40; L.wide_w_hi = (L.wfr_cols - 2 * 8 - 1) / 2;
-          { const int lo_ = opt_int("ABPOA_HIP_WIDE_LO", 0); if (lo_ > 0) L.wide_w_lo = lo_; }
-          const int rr_ = opt_int("ABPOA_HIP_RING_ROWS", 0); const bool rr_env_ = rr_ >= 4;
-          if (rr_env_) L.wfr_rows = rr_ >= 16 ? 16 : (rr_ >= 8 ? 8 : 4);
-          // (up to 120 KB per wavefront: a convex int32 ring of 16 rows is 58 KB; above 64 KB the launch raises the kernel's dynamic-LDS limit)
-          const int budget = 120 * 1024 - L.w_phase_off - 512;
-          while ((int64_t)L.wfr_rows * fww * (L.wfr_cols + 4) * 4 > budget && L.wfr_rows > 4) L.wfr_rows /= 2;
-          // One wavefront per alignment: LDS is what limits how many alignments a CU holds.  It is handed out in pieces of 1280 B, 128 per CU
-          // (tools/probes/lds_granule.hip: 3 x 53760 B fit a CU, 3 x 54080 B do not, whatever the occupancy query says).  The deepest ring with which
-          // the whole launch is resident, counting at most eight workgroups per CU -- two wavefronts per SIMD, which is what the registers allow and
-          // what pays: a SIMD with two alignments to issue from does 1.6x the rows of one with a single wavefront (tools/two_waves_probe.py).  A
-          // shallower ring sends more rows to the HBM gather (predecessor older than the ring: 0.5 % / 14 % / ~45 % of the rows of a 15 %-error
-          // graph at depth 16 / 8 / 4; rows +1.6 % / +6.5 %).
-          const int extra_ = L.wide_nw > 1 ? 16 * 16 + 64 : 0;      // (exchange slots: teams only)
-          auto per_cu_ = [&](int rows_) { return std::min<int64_t>(WIDE_PER_CU_MAX, 128 / ((L.w_phase_off + (int64_t)rows_ * fww * (L.wfr_cols + 4) * 4 + extra_ + 1279) / 1280)); };
-          if (!(rr_env_)) {
-              const int top_ = L.wfr_rows; int best_ = top_;
-              for (int r_ = top_; r_ >= WIDE_RING_MIN; r_ /= 2) {
-                  if (per_cu_(r_) > per_cu_(best_)) best_ = r_;
-                  if (per_cu_(r_) * 256 >= std::min(n_aln, WIDE_PER_CU_MAX * 256)) { best_ = r_; break; }
-              }
-              L.wfr_rows = best_;
-          }
-          L.wx_off = L.fr_off + (int)align_up((size_t)L.wfr_rows * fww * (L.wfr_cols + 4) * 4, 16);
-          L.total_wide = L.w_phase_off + L.wx_off + extra_;
-          if (P == 1) L.wide_nw = 0;      // (linear gaps: the narrow loop only -- dp_common.h takes_fast)
-      } }
+    // the depth.
+    L.wide_on = 0; L.wfr_rows = L.wfr_cols = L.wx_off = L.total_wide = 0; L.wide_w_lo = 1; L.wide_w_hi = 0; L.narrow_off = 0; L.w_mx_off = L.w_phase_off = 0;
+    if (L.fr_cols && L.q_cap && !opt_on("ABPOA_HIP_NOWIDE")) {
+        L.wide_on = 1;
+        // (rows wider than the 448-column ring -- reads of 20 kb and more: w = 10 + 0.01 L -- take the kernel's long-read form: 704 columns, 8 - 11 chunks a row)
+        L.wfr_cols = (est_cols > WIDE_RING_COLS && !opt_on("ABPOA_HIP_NOXL")) ? WIDE_RING_COLS_XL : WIDE_RING_COLS; L.wfr_rows = 16;
+        if (sc->m > 16) L.wide_on = 0;      // (4-bit query codes)
+        L.w_mx_off = (int)align_up((size_t)(max_qlen + 2) / 2, 16); L.w_phase_off = L.w_mx_off + (int)align_up(4 * sc->m * (sc->m + 1), 16);
+        // ring words per column of the wide kernels: as the narrow loop's, but two instead of three for convex int32 (rows_fast.h EPACK: E as 16-bit
+        // differences to H, which needs gap-open + extend <= 65535)
+        const int fww = (P == 5 && max_bits == 32) ? 2 : fw;
+        if (P == 5 && (sc->gap_open1 + sc->gap_ext1 >= 65535 || sc->gap_open2 + sc->gap_ext2 >= 65535)) L.wide_on = 0;      // (0xffff: "E is inf" in the compact spill records)
+        L.wide_w_lo = 40; L.wide_w_hi = (L.wfr_cols - 2 * 8 - 1) / 2;
+        { const int lo_ = opt_int("ABPOA_HIP_WIDE_LO", 0); if (lo_ > 0) L.wide_w_lo = lo_; }
+        const int rr_ = opt_int("ABPOA_HIP_RING_ROWS", 0); const bool rr_env_ = rr_ >= 4;
+        if (rr_env_) L.wfr_rows = rr_ >= 16 ? 16 : (rr_ >= 8 ? 8 : 4);
+        // (up to 120 KB per wavefront: a convex int32 ring of 16 rows is 58 KB; above 64 KB the launch raises the kernel's dynamic-LDS limit)
+        const int budget = 120 * 1024 - L.w_phase_off - 512;
+        while ((int64_t)L.wfr_rows * fww * (L.wfr_cols + 4) * 4 > budget && L.wfr_rows > 4) L.wfr_rows /= 2;
+        // One wavefront per alignment: LDS is what limits how many alignments a CU holds.  It is handed out in pieces of 1280 B, 128 per CU
+        // (tools/probes/lds_granule.hip: 3 x 53760 B fit a CU, 3 x 54080 B do not, whatever the occupancy query says).  The deepest ring with which
+        // the whole launch is resident, counting at most eight workgroups per CU -- two wavefronts per SIMD, which is what the registers allow and
+        // what pays: a SIMD with two alignments to issue from does 1.6x the rows of one with a single wavefront (tools/two_waves_probe.py).  A
+        // shallower ring sends more rows to the HBM gather (predecessor older than the ring: 0.5 % / 14 % / ~45 % of the rows of a 15 %-error
+        // graph at depth 16 / 8 / 4; rows +1.6 % / +6.5 %).
+        auto per_cu_ = [&](int rows_) { return std::min<int64_t>(WIDE_PER_CU_MAX, 128 / ((L.w_phase_off + (int64_t)rows_ * fww * (L.wfr_cols + 4) * 4 + 1279) / 1280)); };
+        if (!(rr_env_)) {
+            const int top_ = L.wfr_rows; int best_ = top_;
+            for (int r_ = top_; r_ >= WIDE_RING_MIN; r_ /= 2) {
+                if (per_cu_(r_) > per_cu_(best_)) best_ = r_;
+                if (per_cu_(r_) * 256 >= std::min(n_aln, WIDE_PER_CU_MAX * 256)) { best_ = r_; break; }
+            }
+            L.wfr_rows = best_;
+        }
+        L.wx_off = L.fr_off + (int)align_up((size_t)L.wfr_rows * fww * (L.wfr_cols + 4) * 4, 16);
+        L.total_wide = L.w_phase_off + L.wx_off;
+        if (P == 1) L.wide_on = 0;      // (linear gaps: the narrow loop only -- dp_common.h takes_fast)
+    }
 }
 
 int wide_workgroups_per_cu(int total_wide) { return std::min(WIDE_PER_CU_MAX, 128 / ((total_wide + 1279) / 1280)); }
@@ -151,7 +140,7 @@ int wide_sets_per_cu(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_
     if (max_qlen <= 0) return 0;
     const int w_max = sc->wb + (int)(sc->wf * (float)max_qlen);
     LdsPlan pl; estimate_lds(sc, 3 * max_qlen + 1024, max_qlen, true, n_sets, &pl);
-    if (pl.wide_nw != 1 || !(w_max >= pl.wide_w_lo && w_max <= pl.wide_w_hi) || pl.total_wide <= 0) return 0;
+    if (!takes_wide_band(pl, w_max) || pl.total_wide <= 0) return 0;
     // (LDS is handed out in pieces of 1280 B, 128 per CU: tools/probes/lds_granule.hip; 166-192 VGPRs: two wavefronts per SIMD at most)
     return std::max(1, wide_workgroups_per_cu(pl.total_wide));
 }
@@ -199,9 +188,9 @@ void choose_kernels(DevicePlan &P, int n_sets, const abpoa_hip_readset_t *sets, 
     P.out_cap = P.roomy ? std::max((int)POA_OUT_CAP, std::min(250, P.max_reads + 1)) : POA_OUT_CAP;
     P.dir = !P.local && !P.extend && !P.general && !P.amb && P.in_cap <= POA_IN_CAP && dir_words_allowed(sc);
     // band half-widths that take the wide row loop (LdsPlan.wide_w_lo / hi; none when the wide kernels are off), depth of its score ring
-    P.wide_lo = 1; P.wide_hi = 0; P.wide_ring_rows = 16; P.wide_nw = P.wfr_cols = 0;
+    P.wide_lo = 1; P.wide_hi = 0; P.wide_ring_rows = 16; P.wide_on = P.wfr_cols = 0;
     { LdsPlan pl; estimate_lds(sc, 3 * P.max_qlen + 1024, P.max_qlen, banded, n_sets, &pl);
-      if (pl.wide_nw >= 1 && !P.local && !P.general) { P.wide_lo = pl.wide_w_lo; P.wide_hi = pl.wide_w_hi; P.wide_ring_rows = pl.wfr_rows; P.wide_nw = pl.wide_nw;
+      if (pl.wide_on >= 1 && !P.local && !P.general) { P.wide_lo = pl.wide_w_lo; P.wide_hi = pl.wide_w_hi; P.wide_ring_rows = pl.wfr_rows; P.wide_on = pl.wide_on;
               P.wfr_cols = pl.wfr_cols; } }
 }
 

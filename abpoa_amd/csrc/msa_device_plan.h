@@ -21,10 +21,10 @@ struct DevicePlan {
     // may take the job (msa_device.cpp plan_rounds decides)
     bool general, fast_local, dir, lin_fast, rounds_possible;
     bool roomy; int in_cap, out_cap;      // the last pass of the ladder: an edge slot per read at every node
-    // band half-widths that take the wide row loop (LdsPlan.wide_w_lo / hi; none when the wide kernels are off), depth of its score ring.  wide_nw / wfr_cols:
-    // wavefronts per alignment and ring columns of the ESTIMATE the range comes from (0 where the job has no wide loop) -- kept for the CPU test alone; no
-    // driver stage reads them, the launch's final values are DevBatch.lds.wide_nw / wfr_cols (msa_device.cpp final_lds_plan)
-    int wide_lo, wide_hi, wide_ring_rows, wide_nw, wfr_cols;
+    // band half-widths that take the wide row loop (LdsPlan.wide_w_lo / hi; none when the wide kernels are off), depth of its score ring.  wide_on / wfr_cols:
+    // the wide loop's switch and ring columns of the ESTIMATE the range comes from (0 where the job has no wide loop) -- kept for the CPU test alone; no
+    // driver stage reads them, the launch's final values are DevBatch.lds.wide_on / wfr_cols (msa_device.cpp final_lds_plan)
+    int wide_lo, wide_hi, wide_ring_rows, wide_on, wfr_cols;
     // ragged sets: extra columns per set, the part of them that counts for the choice of the row loop, the largest, the effective band half-widths
     std::vector<int> extra, route; int max_extra, weff_lo, weff_hi;
     bool dir_wide, dir_wide_auto, any_wide_set;      // direction words for the wide-band sets too / ABPOA_HIP_DIR_WIDE leaves that to the driver / a set takes the wide loop

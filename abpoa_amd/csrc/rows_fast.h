@@ -101,7 +101,7 @@ __device__ __forceinline__ void slow_f_vectors(int vbase, int end_sn, int max_pr
 #endif
 // Timing-only ablation switches (tools/kernel_bench.py with ABPOA_HIP_DBG=bits on the "prof" build): results are wrong on purpose.
 // Diagnostic builds (-DABPOA_HIP_WIDE_COUNTERS, with ABPOA_HIP_DBG=128 so that the tail keeps them): rows per path of the wide loop in AlnOut.seg --
-// 0 wide body, 1 not eligible (predecessor count / distance), 2 ring / geometry, 3 wider than NW chunks, 4 slow vectors span two wavefronts, 5 wrap guard
+// 0 wide body, 1 not eligible (predecessor count / distance), 2 ring / geometry, 3 wider than the body's chunks, 4 slow vectors span two wavefronts, 5 wrap guard
 // -DABPOA_HIP_ROW_CENSUS (same hand-over): rows and clock ticks per body of the NARROW loop -- seg[i] = rows << 40 | ticks for i = 0 one predecessor
 // (tight loop), 1 two predecessors (tight loop), 2 three / four predecessors (straight-line body), 3 the exact bodies (fast / general); 4 = tile switches
 #ifdef ABPOA_HIP_ASM_CENSUS      // (-DABPOA_HIP_ROW_CENSUS -DABPOA_HIP_ASM_CENSUS: the census WITH the assembly loop -- slot 0 = its rows, slot 1 = the C++ copies of the one- / two-predecessor body)
@@ -129,7 +129,7 @@ __device__ __forceinline__ void slow_f_vectors(int vbase, int end_sn, int max_pr
 #else
 #define ABL(BIT) false
 #endif
-template <typename T, int GAP, int NW = 1, bool WIDEB = false, bool DIR = false, bool XL = false>
+template <typename T, int GAP, bool WIDEB = false, bool DIR = false, bool XL = false>
 __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, const FastIO<T> &io, const uint8_t *s_query,
                                           long long &cursor_out, long long &n_cells_out, int &status, int &rows_done_out, int &last_done, long long *fseg, int *best_out = nullptr) {
 #ifdef ABPOA_HIP_PROFILE
@@ -145,47 +145,40 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
     constexpr bool CSP = DIR && WIDEB;
     constexpr int CWR = CSP ? (I16 ? (GAP == 2 ? 4 : 2) : 2) : CW;
     constexpr bool CPK = CSP && !I16 && GAP == 2;
-    static_assert(!(DIR && NW > 1), "teams of wavefronts keep the score-record arenas");
-    static_assert(!(GAP == 0 && (DIR || NW > 1 || WIDEB)), "linear gaps: the narrow loop with H records only");
+    static_assert(!(GAP == 0 && (DIR || WIDEB)), "linear gaps: the narrow loop with H records only");
     constexpr int DB = DirFmt<T, GAP>::DB, CAPF1 = GAP == 1 ? DIRA_CAP1 : DIRC_CAP1, CAPF2 = DIRC_CAP2;
     auto dir_units = [](int nv) __attribute__((always_inline)) { return DirFmt<T, GAP>::units(nv); };
     // arena units of a row of nv vectors (spill: the row also keeps its score records)
     auto row_units = [&](int nv, bool spill) __attribute__((always_inline)) { return DIR ? dir_units(nv) + (spill ? nv * CWR : 0) : nv * CW; };
     bool row_spill = false;                          // (DIR) the current row keeps its score records: set by the row loop before a body runs
-    constexpr bool WPLAN = NW > 1 || WIDEB;          // the wide kernels have their own score ring (LdsPlan wfr_*)
+    // (WIDEB: the wide kernels have their own score ring, LdsPlan wfr_*)
     // Ring words per column.  int16: H | E1 << 16, E2.  int32: H, E1, E2 -- but in the wide kernels' convex ring (EPACK) H and ONE word of differences
     // (H - E1) | (H - E2) << 16: E leaving a cell is max(Ein - e, H - oe) with Ein <= H, so H - E is in [e, oe] wherever H is a score, and 0 stands for
     // "both inf" where H is inf (outside the band, padding).  Two words instead of three: a ring of 8 rows for a 10 kb convex alignment is 29 KB, and
     // four workgroups share a CU (40 KB each) instead of three.  Row 0 -- E = inf beside real H -- stays out of such a ring: its successors read its records.
-    constexpr bool EPACK = WPLAN && !I16 && GAP == 2;
+    constexpr bool EPACK = WIDEB && !I16 && GAP == 2;
     constexpr int NPW = I16 ? (GAP == 2 ? 2 : 1) : (GAP == 2 ? (EPACK ? 2 : 3) : (GAP == 0 ? 1 : 2));      // (linear gaps: H alone; int16: in the low half of the word)
     constexpr int PL_E1 = 1, PL_E2 = 2, PL_F1 = GAP == 1 ? 2 : 3, PL_F2 = 4;
     constexpr int GEO_RING = 1 << 24;
     const int lane = threadIdx.x & 63, l = lane % PN, vvl = lane / PN;
-    const int wid = NW > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;      // wavefront of the workgroup = 64-column chunk of a wide row
-    const int tid = NW > 1 ? (int)threadIdx.x : lane;
-    constexpr int NT = NW * 64;
     const int gn = d.n_rows, qlen = d.qlen, m = b.m, m1 = b.m + 1, w = d.w;
     const int inf = d.inf_min;
     const int e1 = b.e1, o1 = b.o1, oe1 = b.o1 + b.e1, e2 = b.e2, o2 = b.o2, oe2 = b.o2 + b.e2;
-    // (the single-wave wide kernel's ring width is a compile-time constant: address offsets and clamps fold into the instructions)
-    const int RR = WPLAN ? b.lds.wfr_rows : b.lds.fr_rows, RC = WIDEB ? (XL ? WIDE_RING_COLS_XL : WIDE_RING_COLS) : (WPLAN ? b.lds.wfr_cols : b.lds.fr_cols), RCS = RC + 4;
+    // (the wide kernel's ring width is a compile-time constant: address offsets and clamps fold into the instructions)
+    const int RR = WIDEB ? b.lds.wfr_rows : b.lds.fr_rows, RC = WIDEB ? (XL ? WIDE_RING_COLS_XL : WIDE_RING_COLS) : b.lds.fr_cols, RCS = RC + 4;
     // (the wide kernels have their own carve-up of the LDS: the query packed two codes to a byte -- LdsPlan.w_*)
-    const int ph_off = WPLAN ? b.lds.w_phase_off : b.lds.phase_off;
+    const int ph_off = WIDEB ? b.lds.w_phase_off : b.lds.phase_off;
     int *fr = (int *)(lds_raw + ph_off + b.lds.fr_off);
-    // wide rows: exchange slots (two parities x 8 entries of 16 bytes) and the hand-over record of a row done by wavefront 0 alone
-    int4 *xch = (int4 *)(lds_raw + ph_off + b.lds.wx_off);
-    int *bcast = (int *)(xch + 16);
     // LDS byte address of ring row (r & (RR - 1)), column 0, held by lane r & 63: RR divides 64, so one lane-constant VGPR serves
     // every row -- a v_readlane replaces the and / mul / shift / add chain per predecessor and for the row's own slot
     typedef __attribute__((address_space(3))) int lds_int_t;
     const int vslot = (int)(unsigned)(size_t)(lds_int_t *)fr + 4 * ((threadIdx.x & 63 & (RR - 1)) * (NPW * RCS) + 2);
     auto ring_at = [&](int slot_addr, int col_idx) __attribute__((always_inline)) { return (const int *)(lds_int_t *)(size_t)(unsigned)(slot_addr + 4 * col_idx); };
-    int *s_mx = (int *)(lds_raw + (WPLAN ? b.lds.w_mx_off : b.lds.mx_off));
+    int *s_mx = (int *)(lds_raw + (WIDEB ? b.lds.w_mx_off : b.lds.mx_off));
     // query code of base j (0-based): plain bytes, or -- wide kernels -- two 4-bit codes to a byte (ten thousand bases in 5 KB: with a 4-row ring an
     // alignment then needs under 20 KB of LDS, eight workgroups share a CU and every SIMD has two wavefronts to issue from)
     auto qat = [&](int j) __attribute__((always_inline)) -> int {
-        if constexpr (WPLAN) return ((int)s_query[j >> 1] >> ((j & 1) * 4)) & 15; else return (int)s_query[j];
+        if constexpr (WIDEB) return ((int)s_query[j >> 1] >> ((j & 1) * 4)) & 15; else return (int)s_query[j];
     };
     const int infw = I16 ? (int)(((unsigned)inf & 0xffffu) | ((unsigned)inf << 16)) : inf;
     const int qlen_sn = qlen / PN;
@@ -202,9 +195,8 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
     const int ktie = argmax_tie32(PN, l, vvl);                                          // int32 wide rows: residue, then the end vector, then the vector order
 
     // ---- LDS: extended score matrix (column m = 0) and the score ring, everything "inf"
-    { GLOBAL_AS const int32_t *g_mat = vgpr_ptr(b.mat); for (int i = tid; i < m * m1; i += NT) { const int bb = i / m1, qc = i - bb * m1; s_mx[i] = qc < m ? g_mat[bb * m + qc] : 0; } }
-    for (int i = tid; i < RR * NPW * RCS; i += NT) { const int pl = (i / RCS) % NPW; fr[i] = (I16 && pl == 0) ? infw : ((EPACK && pl == 1) ? 0 : inf); }
-    if (NW > 1 && tid < 16) xch[tid] = make_int4(INT_MIN, INT_MIN, I16 ? 0 : INT_MIN, 0);      // entries of absent wavefronts stay neutral
+    { GLOBAL_AS const int32_t *g_mat = vgpr_ptr(b.mat); for (int i = lane; i < m * m1; i += 64) { const int bb = i / m1, qc = i - bb * m1; s_mx[i] = qc < m ? g_mat[bb * m + qc] : 0; } }
+    for (int i = lane; i < RR * NPW * RCS; i += 64) { const int pl = (i / RCS) % NPW; fr[i] = (I16 && pl == 0) ? infw : ((EPACK && pl == 1) ? 0 : inf); }
     WG_SYNC();
     auto ring_put = [&](int slot, int x, int H, int E1, int E2) __attribute__((always_inline)) {
         int *q = fr + slot * (NPW * RCS) + 2 + x;
@@ -232,7 +224,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         if ((long long)W0 * CWR > d.plane_cap) { status = ABPOA_HIP_STATUS_OVERFLOW; cursor_out = 0; n_cells_out = 0; rows_done_out = 0; return; }
         const bool ring0 = W0 <= RC && !EPACK;
         T *H = io.planes;
-        for (int i = tid; i < W0; i += NT) {
+        for (int i = lane; i < W0; i += 64) {
             int h, x1 = inf, x2 = inf, f1 = inf, f2 = inf;
             if (GAP == 0) h = wr(-e1 * i);      // (reference :553-607 lg_first_row)
             else if (GAP == 1) { const int g = wr(-o1 - e1 * i); h = i == 0 ? 0 : g; x1 = i == 0 ? wr(-oe1) : inf; f1 = i == 0 ? inf : g; }
@@ -253,7 +245,6 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         cur = (end_sn0 + 1) * CWR;
         // (DIR: a row's offset is that of its -- here absent -- words, its records sit in front of them) // source: successors get left = right = 1 (:556-561)
         if (lane == 0) { vg_geo = (end_sn0 << 12) | (ring0 ? GEO_RING : 0); vg_mi = 0; vg_off = DIR ? cur : 0; }
-        if (NW > 1) WG_SYNC();               // ring row 0 was written by every wavefront
     }
 
     // ------------------------------------------------------------------ static metadata, two tiles ahead
@@ -283,7 +274,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
 #pragma unroll
         for (int k = 0; k < 4; ++k) { const int dk = myrow - b1.p[k]; fastrow = fastrow && dk >= 1 && dk < RR; }
         tv_meta = (a1.base & 0xff) | (imin(np, 255) << 8) | (fastrow ? (1 << 16) : 0);
-        if (!WPLAN) {
+        if (!WIDEB) {
             tv_meta |= ((fastrow && np <= 2 && RC <= 128) ? (1 << 17) : 0) | ((fastrow && np >= 3 && RC <= 128) ? (1 << 18) : 0);      // bit 17: straight-line body (pads 128 ring columns)
             bool row8 = np >= 5 && np <= 8 && myrow < gn - 1 && myrow >= 1 && RC <= 128;      // bit 20: five to eight predecessors, all in the score ring: the straight-line body's widest copy
 #pragma unroll
@@ -293,7 +284,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         {                                            // bit 19: the row may take the all-chunks body (1..8 predecessors, all inside the 64-row geometry ring)
             bool widerow = np >= 1 && np <= 8 && myrow < gn - 1 && myrow >= 1;
 #pragma unroll
-            for (int k = 0; k < NPM; ++k) { const int dk = myrow - b1.p[k]; widerow = widerow && dk >= 1 && dk < ((WIDEB || !WPLAN) ? 64 : RR); }      // (single-wave loops: older ones come from HBM)
+            for (int k = 0; k < NPM; ++k) { const int dk = myrow - b1.p[k]; widerow = widerow && dk >= 1 && dk < 64; }      // (older than the score ring: from HBM)
             tv_meta |= widerow ? (1 << 19) : 0;
         }
         if constexpr (DIR) {      // bit 21: a successor beyond the score ring (or the sink) will read this row's H / E from HBM: it keeps its score records.
@@ -849,9 +840,8 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         if constexpr (GAP == 0) return turbo_lin(npc, slowc, row, ti); else return turbo_aff(npc, slowc, row, ti);
     };
 
-    constexpr int NWP = NW <= 2 ? 2 : (NW <= 4 ? 4 : 8);            // exchange entries read per lane group
     // ---- MULTI-CHUNK body for wide bands (10 kb reads: 240-300 columns = 4-5 chunks of 64; where a read drifts against the graph the band
-    //      opens to 6, seldom 7 chunks for thousands of rows -- three instantiations: 2-3, 4-5 and 6-7 chunks): every chunk of the row is in registers at once.
+    //      opens to 6, seldom 7 chunks for thousands of rows -- one instantiation per chunk count from 4 on, see the row loop): every chunk of the row is in registers at once.
     //      The lane owns column (64 c + lane) of each chunk c, so the chunks are independent instruction streams that the scheduler interleaves
     //      (LDS reads of all chunks in flight together, DPP scans of all chunks back to back without wait states), and everything that is
     //      per row -- band, conditions, arg-max reduction, commit -- is paid once for ~250 columns instead of once per 64.
@@ -859,14 +849,10 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
     //      seed[0] = first - e, seed[c+1] = max(total[c], seed[c]) - 64 e, F = max(S, seed) - cf  (chunk_tail's closed form, carried in H units).
     //      The arg-max is taken from max(M + q, E): an F term is some H of the same row minus at least o + e (reference :870-874 / :990-997).
     //      ilp_band: 0 = not applicable, -2 = arena overflow, else the number of chunks; ilp_chunks: 0 = not applicable (nothing touched), 1 = done.
-    //      TEAMS (NW > 1 wavefronts per alignment): every wavefront runs the same row loop on its own copy of the per-row registers and takes a
-    //      contiguous share of the row's chunks (c0 .. c0 + cnt - 1); ONE exchange through LDS per row carries each wavefront's carry-chain result
-    //      (seed out of its last chunk, computed as if nothing came in: the chain is max-plus, the incoming seed is folded in afterwards), its
-    //      arg-max key and its wrap flag; a second barrier at the end of the row publishes the ring slot.
+    //      One wavefront per alignment owns every chunk of the row.
     constexpr int NCHX = XL ? 11 : 7;      // (XL: the long-read form of the wide kernel, 704-column ring, one wavefront per SIMD's worth of registers)
-    constexpr bool TEAM = NW > 1;
     int two_chunk_streak = 0;                                       // (narrow kernel) the last row took the two-chunk body with a band of 65-128 columns: the next one tries it first
-    int qcx_beg_sn = -1, qcx_c0 = -1, qoffx[NCHX] = {};            // cached query codes of this lane's column in every chunk of this wavefront, for band start qcx_beg_sn
+    int qcx_beg_sn = -1, qoffx[NCHX] = {};                          // cached query codes of this lane's column in every chunk of the row, for band start qcx_beg_sn
     int ilp_far = 0;                                                // bit k: predecessor k of the row is not in the score ring (older than its depth, or a row too wide for it): HBM gather
     auto ilp_band = [&](int row, int ti) __attribute__((always_inline)) -> int {
         int mn_mi, mx_mi, min_pb;
@@ -895,12 +881,9 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
     auto ilp_chunks = [&](auto nchc, int nch, int row, int ti) __attribute__((always_inline)) -> int {
         constexpr int NCH = decltype(nchc)::value;
         const int Wr = (end_sn - beg_sn + 1) * PN;
-        // this wavefront's chunks: c0 .. c0 + cnt - 1 (one wavefront: all of them; teams: nch / NW each, the first nch % NW one more)
-        int c0 = 0, cnt = nch;
-        if (TEAM) team_chunks(nch, NW, wid, c0, cnt);
-        const int colb = beg_sn * PN + lane + 64 * c0;              // this lane's column in the wavefront's first chunk
-        if (__builtin_expect(beg_sn != qcx_beg_sn || (TEAM && c0 != qcx_c0), 0)) {
-            qcx_beg_sn = beg_sn; qcx_c0 = c0;
+        const int colb = beg_sn * PN + lane;                        // this lane's column in the row's first chunk
+        if (__builtin_expect(beg_sn != qcx_beg_sn, 0)) {
+            qcx_beg_sn = beg_sn;
 #pragma unroll
             for (int c = 0; c < NCHX; ++c) { const int col = colb + 64 * c; qoffx[c] = (col >= 1 && col <= qlen) ? qat(col - 1) : m; }
         }
@@ -934,7 +917,6 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             // (DIR: the predecessor kept its score records -- tile bit 21 / a row too wide for the ring -- in front of its direction words)
             const T *Hp = io.planes + (long long)(uint32_t)(__builtin_amdgcn_readlane(vg_off, p & 63) - (DIR ? (((g_ >> 12) & 0xfff) - pb + 1) * CWR : 0)) * PN;
             gld_wait();                                              // (earlier score-plane stores of this wave are complete)
-            if (TEAM) lds_barrier();                                 // (... and of the other wavefronts of the team: the far flag is the same in all of them)
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 const int x = colb + 64 * c - pb * PN, xh = med3i(x - 1, 0, Wp - 1), xe = med3i(x, 0, Wp - 1);
@@ -1004,7 +986,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             lowest = imin(lowest, h[c]);
         }
         const bool wrap_here = __any(lowest < fast_lo);
-        if (!TEAM && __builtin_expect(wrap_here, 0)) return 0;
+        if (__builtin_expect(wrap_here, 0)) return 0;
         // ---- unseeded prefix maxima per chunk, all chains interleaved
         int g1[NCH], g2[NCH], s1[NCH], s2[NCH];
 #pragma unroll
@@ -1017,13 +999,13 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         const int relv_end = end_sn - beg_sn;
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            const int cg = c0 + c, vb = beg_sn + cg * NV;          // chunk index in the row
+            const int vb = beg_sn + c * NV;
             // (the end vector is in the last chunk)
-            const bool in_band = (!TEAM && c < NCH - 2) ? true : cg * 64 + lane < Wr, is_end = (!TEAM && c < NCH - 2) ? false : (cg * NV + vvl == relv_end);
+            const bool in_band = c < NCH - 2 ? true : c * 64 + lane < Wr, is_end = c < NCH - 2 ? false : (c * NV + vvl == relv_end);
             int cand = hsE[c]; if (end_sn == qlen_sn) cand = (is_end && colb + 64 * c > qlen) ? inf : cand;
             unsigned key;
             if (I16) key = argmax_key16(cand, kconst, vb, is_end);
-            else key = argmax_key32(cand, vfloor, ktie, cg, NV, is_end);
+            else key = argmax_key32(cand, vfloor, ktie, c, NV, is_end);
             amk = (in_band && key > amk) ? key : amk;
         }
         // interleaved DPP chains: F scans of every chunk + the arg-max key
@@ -1044,59 +1026,26 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             step(std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xA>{});
             step(std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xC>{});
         }
-        unsigned kbst = (unsigned)__builtin_amdgcn_readlane((int)amk, 63);
+        const unsigned kbst = (unsigned)__builtin_amdgcn_readlane((int)amk, 63);
         FSTAMP(2)
-        // ---- carry chain over the chunk totals (scalar), then F of every chunk.  seed[c] = "first - e" of chunk c; seed[c + 1] = max(total[c], seed[c]) - 64 e.
-        //      Wavefront 0 (or the only one) starts from the row's first column; the others start from "nothing" (INT_MIN: total[c] always wins the
-        //      max, so nothing wraps) and fold the seed that comes in from the wavefronts before them after the exchange.
-        //      (one wavefront: the chain runs in the vector unit on wave-uniform values -- the totals are read out of lane 63 back to back and the
+        // ---- carry chain over the chunk totals, then F of every chunk.  seed[c] = "first - e" of chunk c; seed[c + 1] = max(total[c], seed[c]) - 64 e.
+        //      (the chain runs in the vector unit on wave-uniform values -- the totals are read out of lane 63 back to back and the
         //       dependent max / subtract steps need no trip through the scalar unit)
         int seed1[NCH + 1], seed2[NCH + 1];
-        seed1[0] = (!TEAM || wid == 0) ? __builtin_amdgcn_readlane(h[0], 0) - e1 : INT_MIN; seed2[0] = (!TEAM || wid == 0) ? seed1[0] + e1 - e2 : INT_MIN;
-        if (!TEAM) { asm("" : "+v"(seed1[0])); if (GAP == 2) asm("" : "+v"(seed2[0])); }
+        seed1[0] = __builtin_amdgcn_readlane(h[0], 0) - e1; seed2[0] = seed1[0] + e1 - e2;
+        asm("" : "+v"(seed1[0])); if (GAP == 2) asm("" : "+v"(seed2[0]));
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             seed1[c + 1] = carry_next(__builtin_amdgcn_readlane(imax(s1[c], g1[c]), 63), seed1[c], e1);
             if (GAP == 2) seed2[c + 1] = carry_next(__builtin_amdgcn_readlane(imax(s2[c], g2[c]), 63), seed2[c], e2); else seed2[c + 1] = INT_MIN;
         }
-        if constexpr (TEAM) {
-            // exchange entry of this wavefront: {chain result out of its last chunk (two planes), arg-max key, wrap flag}
-            int out1 = seed1[0], out2 = seed2[0];
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) if (c < cnt) { out1 = seed1[c + 1]; out2 = seed2[c + 1]; }
-            int4 *xs = xch + (row & 1) * 8;
-            if (lane == 0) xs[wid] = make_int4(out1, out2, cnt > 0 ? (int)kbst : 0, wrap_here && cnt > 0 ? 1 : 0);
-            lds_barrier();
-            const int4 en = xs[lane & (NWP - 1)];
-            // incoming seed: fold the entries of the wavefronts before this one in order (saturating: INT_MIN stays "nothing")
-            int in1 = INT_MIN, in2 = INT_MIN, anywrap = 0; unsigned kall = 0;
-#pragma unroll
-            for (int j = 0; j < NW; ++j) {
-                const int a1 = __builtin_amdgcn_readlane(en.x, j), a2 = __builtin_amdgcn_readlane(en.y, j);
-                const unsigned kj = (unsigned)__builtin_amdgcn_readlane(en.z, j);
-                anywrap |= __builtin_amdgcn_readlane(en.w, j); kall = kj > kall ? kj : kall;
-                if (j < wid) {
-                    int c0j, cntj; team_chunks(nch, NW, j, c0j, cntj);
-                    in1 = carry_fold(a1, in1, cntj * 64 * e1); in2 = carry_fold(a2, in2, cntj * 64 * e2);
-                }
-            }
-            if (__builtin_expect(anywrap, 0)) return 0;
-            kbst = kall;
-            if (wid > 0) {
-#pragma unroll
-                for (int c = 0; c < NCH; ++c) {
-                    seed1[c] = carry_fold(seed1[c], in1, c * 64 * e1);
-                    if (GAP == 2) seed2[c] = carry_fold(seed2[c], in2, c * 64 * e2);
-                }
-            }
-        }
         if (!I16) { if (__builtin_expect(argmax_declines32(kbst), 0)) return 0; }
         FSTAMP(3)
         // ---- from here on the row is committed
-        T *const Hrow = io.planes + (long long)cur * PN + (long long)(lane + 64 * c0) * CWR;
+        T *const Hrow = io.planes + (long long)cur * PN + (long long)lane * CWR;
         off_pn = cur + ((DIR && row_spill) ? (end_sn - beg_sn + 1) * CWR : 0); cur += row_units(end_sn - beg_sn + 1, row_spill);
-        char *const Drow = (char *)io.planes + (size_t)off_pn * 32 + (size_t)(lane + 64 * c0) * DB;      // (DIR) this lane's direction word in the wavefront's first chunk
-        int *const qd = (int *)ring_at(__builtin_amdgcn_readlane(vslot, ti) + 4 * (lane + 64 * c0), 0);
+        char *const Drow = (char *)io.planes + (size_t)off_pn * 32 + (size_t)lane * DB;      // (DIR) this lane's direction word in the row's first chunk
+        int *const qd = (int *)ring_at(__builtin_amdgcn_readlane(vslot, ti) + 4 * lane, 0);
         // (nch is NCH - 1 or NCH: chunks 0 .. NCH - 3 are full, only the last two need band masks, only the last one a store guard)
         int F1[NCH], F2[NCH], S1[NCH], S2[NCH];
 #pragma unroll
@@ -1106,8 +1055,8 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         }
         if (__builtin_expect(end_sn > max_pe, 0)) {                  // vectors beyond every predecessor's band: literal masked scan, last chunk only
 #pragma unroll
-            for (int c = TEAM ? 0 : NCH - 2; c < NCH; ++c) if (c0 + c == nch - 1) {
-                const int vb = beg_sn + (c0 + c) * NV;
+            for (int c = NCH - 2; c < NCH; ++c) if (c == nch - 1) {
+                const int vb = beg_sn + c * NV;
                 const int nvec = imin(NV, end_sn - vb + 1), nfast = imax(0, imin(nvec, max_pe - vb + 1));
                 int first, first2 = 0;
                 if (nfast > 0) {
@@ -1122,7 +1071,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         }
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
-            const bool in_band = (!TEAM && c < NCH - 2) ? true : (c0 + c) * 64 + lane < Wr;
+            const bool in_band = c < NCH - 2 ? true : c * 64 + lane < Wr;
             int Hout, E1out, E2out = inf, t2a, t2b = 0, en_a = 0;
             if (GAP == 1) {
                 Hout = imax(hsE[c], F1[c]);
@@ -1160,9 +1109,8 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             }
             if (DIR && !row_spill) {}
             else if (DIR && !in_band) {}      // (the row's words start right behind its last record)
-            // (teams: in-band lanes only -- another wavefront owns the cells behind the row's end) one record store per lane, all 64 lanes (lanes past the band write cells the next row overwrites:
-            //  same wave, program order)
-            else if (TEAM ? (c < cnt && in_band) : (c < NCH - 1 || nch == NCH)) {
+            // one record store per lane, all 64 lanes (lanes past the band write cells the next row overwrites: same wave, program order)
+            else if (c < NCH - 1 || nch == NCH) {
                 T *H = Hrow + c * 64 * CWR;
                 if (CSP) {      // compact records (CWR)
                     if (I16 && GAP == 1) *(int *)H = he;
@@ -1175,18 +1123,12 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 else if (GAP == 1) { int4 rec; rec.x = Hout; rec.y = E1out; rec.z = F1[c]; rec.w = mflag; *(int4 *)H = rec; }
                 else { int4 r0, r1; r0.x = Hout; r0.y = E1out; r0.z = E2out; r0.w = F1[c]; r1.x = F2[c]; r1.y = mflag; r1.z = 0; r1.w = 0; ((int4 *)H)[0] = r0; ((int4 *)H)[1] = r1; }
             }
-            if (!TEAM || c < cnt) {
-                if (I16) { qd[c * 64] = in_band ? he : infw; if (GAP == 2) qd[RCS + c * 64] = in_band ? E2out : inf; }
-                else if (EPACK) { qd[c * 64] = in_band ? Hout : inf; qd[RCS + c * 64] = in_band ? (int)((unsigned)(Hout - E1out) | ((unsigned)(Hout - E2out) << 16)) : 0; }
-                else { qd[c * 64] = in_band ? Hout : inf; qd[RCS + c * 64] = in_band ? E1out : inf; if (GAP == 2) qd[2 * RCS + c * 64] = in_band ? E2out : inf; }
-            }
+            if (I16) { qd[c * 64] = in_band ? he : infw; if (GAP == 2) qd[RCS + c * 64] = in_band ? E2out : inf; }
+            else if (EPACK) { qd[c * 64] = in_band ? Hout : inf; qd[RCS + c * 64] = in_band ? (int)((unsigned)(Hout - E1out) | ((unsigned)(Hout - E2out) << 16)) : 0; }
+            else { qd[c * 64] = in_band ? Hout : inf; qd[RCS + c * 64] = in_band ? E1out : inf; if (GAP == 2) qd[2 * RCS + c * 64] = in_band ? E2out : inf; }
         }
         // "inf" up to the ring width
-        if (!TEAM) { for (int c = NCH; c < (RC >> 6); ++c) { qd[c * 64] = infw; if (NPW > 1) qd[RCS + c * 64] = EPACK ? 0 : inf; if (NPW > 2) qd[2 * RCS + c * 64] = inf; } }
-        else {                                                       // (teams: chunk c of the padding is written by wavefront c % NW)
-            int *const qrow = (int *)ring_at(__builtin_amdgcn_readlane(vslot, ti) + 4 * lane, 0);
-            for (int c = nch; c < (RC >> 6); ++c) if (c % NW == wid) { qrow[c * 64] = infw; if (NPW > 1) qrow[RCS + c * 64] = EPACK ? 0 : inf; if (NPW > 2) qrow[2 * RCS + c * 64] = inf; }
-        }
+        for (int c = NCH; c < (RC >> 6); ++c) { qd[c * 64] = infw; if (NPW > 1) qd[RCS + c * 64] = EPACK ? 0 : inf; if (NPW > 2) qd[2 * RCS + c * 64] = inf; }
         FSTAMP(4)
         // ---- row arg-max
         mi = -1;
@@ -1309,12 +1251,11 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         const long long cen_ts = (long long)__builtin_amdgcn_s_memtime();
 #endif
         if (t0 > 0) {       // geometry of the finished tile goes to HBM in one coalesced burst (older predecessors, backtrack, trace)
-            const int rb = t0 - 64 + lane; if (wid == 0) { io.g_bsn[rb] = vg_geo & 0xfff; io.g_esn[rb] = (vg_geo >> 12) & 0xfff; io.g_coff[rb] = (long long)(uint32_t)vg_off * PN;
-                    io.row_max_i[rb] = vg_mi; }
+            const int rb = t0 - 64 + lane; io.g_bsn[rb] = vg_geo & 0xfff; io.g_esn[rb] = (vg_geo >> 12) & 0xfff; io.g_coff[rb] = (long long)(uint32_t)vg_off * PN; io.row_max_i[rb] = vg_mi;
             if (rb >= 1) n_vec_lane += ((vg_geo >> 12) & 0xfff) - (vg_geo & 0xfff) + 1;
             // progress word (backtrack_dir.h): rows below t0 are complete -- their direction words and the geometry above have been acknowledged.  Once per tile,
             // here, where the metadata loads of switch_tile() are about to wait for the same counter; nothing in the per-row path.
-            if constexpr (DIR && NW == 1 && !WIDEB) if (io.prog_a >= 0) {
+            if constexpr (DIR && !WIDEB) if (io.prog_a >= 0) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 *(volatile lds_int_t *)(size_t)(unsigned)io.prog_a = t0;
             }
@@ -1331,7 +1272,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 if (mx > ex_best) { ex_best = mx; ex_i = t0 + ti; ex_j = mi; ex_rem = rem_row; }      // (t0 + ti = the row)
                 else if (b.zdrop > 0) { int dd = (ex_rem - rem_row) - (mi - ex_j); if (dd < 0) dd = -dd; if (ex_best - mx > b.zdrop + e1 * dd) zstop = true; }
             }
-            if constexpr (WPLAN || !I16) {            // (vg_vm: the all-chunks body centres its int32 arg-max keys on the first predecessor's row maximum)
+            if constexpr (WIDEB || !I16) {            // (vg_vm: the all-chunks body centres its int32 arg-max keys on the first predecessor's row maximum)
                 const int vm_new = sgpr(rowmax);
                 asm volatile("s_mov_b32 m0, %8\n\ts_nop 3\n\tv_writelane_b32 %0, %4, m0\n\tv_writelane_b32 %1, %5, m0\n\tv_writelane_b32 %2, %6, m0\n\tv_writelane_b32 %3, %7, m0"
                              : "+v"(vg_geo), "+v"(vg_mi), "+v"(vg_off), "+v"(vg_vm) : "s"(geo_new), "s"(mi), "s"(off_new), "s"(vm_new), "s"(ti) : "m0");
@@ -1341,59 +1282,10 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         };
         int row = imax(t0, 1);
         while (row < r_hi && !zstop) {
-            if constexpr (NW > 1) {
-                // ---- NW wavefronts per alignment: the wide body, else wavefront 0 alone with the single-wave bodies below
-                const int ti = row & 63;
-                last_done = row;
-                const int meta = __builtin_amdgcn_readlane(tv_meta, ti);
-                rterm = __builtin_amdgcn_readlane(tv_rterm, ti);
-                base = meta & 0xff; np = (meta >> 8) & 0xff;
-                int rc = 0;
-                if ((meta >> 19) & 1) {
-                    const int nch_ = ilp_band(row, ti);
-                    if (nch_ == -2) { status = ABPOA_HIP_STATUS_OVERFLOW; break; }
-                    if (nch_ >= 2) rc = ilp_chunks(std::integral_constant<int, (NCHX + NW - 1) / NW>{}, nch_, row, ti);
-                    if (rc != 1) WCOUNT(5);
-                } else WCOUNT(1);
-                if (rc == 1) { WCOUNT(0); commit_row(ti, true); lds_barrier(); ++row; continue; }      // (barrier: the ring slot is complete before any wavefront reads it)
-                rc = 0;
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the HBM gathers of the general body read cells other wavefronts stored
-                lds_barrier();
-                if (wid == 0) {
-                    am_key = 0; am_val = INT_MIN; am_v = 0; am_isend = 0; am_any = false;
-                    rc = general_body(row, ti);
-                    mi = -1;
-                    if (rc == 1) {
-                        if (I16) {
-                            argmax_decode16(wave_max_u32_s(am_key), PN, qlen, inf, rowmax, mi);
-                        } else {
-                            const int vmax = wave_max_i32_s(am_any ? am_val : INT_MIN);
-                            rowmax = vmax;
-                            if (vmax > inf) {
-                                unsigned key = 0;
-                                if (am_any && am_val == vmax) key = ((unsigned)(PN - 1 - l) << 27) | ((unsigned)am_isend << 26) | (0x3FFFFFFu - (unsigned)am_v);
-                                const unsigned kb = wave_max_u32_s(key);
-                                mi = (int)(0x3FFFFFFu - (kb & 0x3FFFFFFu)) * PN + (PN - 1 - (int)(kb >> 27));
-                                if (mi > qlen) mi = -1;
-                            }
-                        }
-                    }
-                    if (lane == 0) { bcast[0] = rc; bcast[1] = beg_sn; bcast[2] = end_sn; bcast[3] = off_pn; bcast[4] = mi; bcast[5] = to_ring ? 1 : 0; bcast[6] = cur; bcast[7] = rowmax; }
-                }
-                lds_barrier();
-                rc = __builtin_amdgcn_readfirstlane(bcast[0]); beg_sn = __builtin_amdgcn_readfirstlane(bcast[1]); end_sn = __builtin_amdgcn_readfirstlane(bcast[2]);
-                off_pn = __builtin_amdgcn_readfirstlane(bcast[3]); mi = __builtin_amdgcn_readfirstlane(bcast[4]); to_ring = __builtin_amdgcn_readfirstlane(bcast[5]) != 0;
-                cur = __builtin_amdgcn_readfirstlane(bcast[6]); rowmax = __builtin_amdgcn_readfirstlane(bcast[7]);
-                if (rc == 2) { status = ABPOA_HIP_STATUS_OVERFLOW; break; }
-                commit_row(ti, to_ring);
-                lds_barrier();                                         // (bcast is free again)
-                ++row;
-                continue;
-            }
             // ---- tight loop over consecutive straight-line rows: only these merge at its back edge (in one loop with the other row
             //      bodies every row paid ~30 register copies for the merge of all paths)
             int ok_ = 1;
-            if constexpr (!WPLAN && GAP != 0) if (__builtin_expect(two_chunk_streak, 0)) {      // the band is 65-128 columns wide at the moment: straight to the two-chunk body
+            if constexpr (!WIDEB && GAP != 0) if (__builtin_expect(two_chunk_streak, 0)) {      // the band is 65-128 columns wide at the moment: straight to the two-chunk body
                 const int ti_ = row & 63, meta_ = __builtin_amdgcn_readlane(tv_meta, ti_);
                 if constexpr (DIR) row_spill = (meta_ >> 21) & 1;
                 if ((meta_ >> 19) & 1) {
@@ -1411,7 +1303,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             // ablation bits / clocks / censuses live in the C++ bodies; ABPOA_HIP_DBG bit 11 keeps the compiler's loop, for comparison.)
             bool cxx_tight = true;
 #if !defined(ABPOA_HIP_ABLATE) && !defined(ABPOA_HIP_PROFILE) && (!defined(ABPOA_HIP_ROW_CENSUS) || defined(ABPOA_HIP_ASM_CENSUS)) && !defined(ABPOA_HIP_NO_ASM_TIGHT)
-            if constexpr (!WPLAN && I16 && GAP == 1 && DIR) {
+            if constexpr (!WIDEB && I16 && GAP == 1 && DIR) {
                 if (asm_tight_on && cur + NV * (r_hi - row) <= cap_turbo) {
                     int code, sM, sTB, sRT, sR2, sP0, sM0, sG0, sSL0, sA, sB, sESN, sBSN, sPB0, sPE0, sNV1, sC0, sP1, sM1, sG1, sSL1, sPB1, sPE1, sP2, sSL2, sPB2, sPE2, sP3, sSL3, sPB3, sPE3;
                     long long inb, amok, msk;
@@ -1439,7 +1331,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 }
             }
 #endif
-            if constexpr (!WPLAN) if (cxx_tight) for (;;) {
+            if constexpr (!WIDEB) if (cxx_tight) for (;;) {
                 const int ti_ = row & 63;
                 const int meta_ = __builtin_amdgcn_readlane(tv_meta, ti_);
                 if (!__builtin_expect((meta_ >> 17) & 1, 1)) break;
@@ -1462,19 +1354,19 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             rterm = __builtin_amdgcn_readlane(tv_rterm, ti);
             base = meta & 0xff; np = (meta >> 8) & 0xff;
             if constexpr (DIR) row_spill = (meta >> 21) & 1;
-            if (!WPLAN && ((meta >> 18) & 1)) {                       // three or four predecessors: the straight-line body, outside the tight loop
+            if (!WIDEB && ((meta >> 18) & 1)) {                       // three or four predecessors: the straight-line body, outside the tight loop
                 if (turbo_body(std::integral_constant<int, 4>{}, std::true_type{}, row, ti) == 1) { commit_row(ti, true); CENSUS(2) ++row; continue; }
             }
-            if (!WPLAN && ((meta >> 20) & 1)) {                       // five to eight predecessors
+            if (!WIDEB && ((meta >> 20) & 1)) {                       // five to eight predecessors
                 if (turbo_body(std::integral_constant<int, 8>{}, std::true_type{}, row, ti) == 1) { commit_row(ti, true); CENSUS(2) ++row; continue; }
             }
             // one or two predecessors and the tight loop declined: most often the row's band reaches one
-            if (!WPLAN && (((meta >> 17) & 1) ? ok_ == 0 : (DIR && ((meta >> 22) & 1)))) {
+            if (!WIDEB && (((meta >> 17) & 1) ? ok_ == 0 : (DIR && ((meta >> 22) & 1)))) {
                                                                       // vector beyond its predecessors' (every PN-th row of a chain) -- the copies that take those vectors
                 const int ok3 = np == 1 ? turbo_body(std::integral_constant<int, 1>{}, std::true_type{}, row, ti) : turbo_body(std::integral_constant<int, 2>{}, std::true_type{}, row, ti);
                 if (ok3 == 1) { commit_row(ti, true); CENSUS(np == 1 ? 0 : 1) ++row; continue; }
             }
-            if (GAP != 0 && !WPLAN && ((meta >> 19) & 1)) {           // narrow kernel, the straight-line bodies declined (a band of 65-128 columns for a stretch of
+            if (GAP != 0 && !WIDEB && ((meta >> 19) & 1)) {           // narrow kernel, the straight-line bodies declined (a band of 65-128 columns for a stretch of
                                                                       // rows, a predecessor beyond the score ring, ...): the all-chunks body with two chunks
                 const int nch_ = ilp_band(row, ti);
                 if (nch_ == -2) { status = ABPOA_HIP_STATUS_OVERFLOW; break; }
@@ -1488,13 +1380,9 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                     // (one body per chunk count from 4 on: a 4-chunk row in the 5-chunk body computes a fifth chunk of lanes nobody keeps -- a fifth of the row's
                     //  vector instructions; 10 kb reads at 5 % error sit at exactly 4 chunks most of the time)
                     if (nch_ <= 3) ok2 = ilp_chunks(std::integral_constant<int, 3>{}, nch_, row, ti);
-#ifndef ABPOA_HIP_WIDE_PAIRED_NCH
                     else if (nch_ == 4) ok2 = ilp_chunks(std::integral_constant<int, 4>{}, nch_, row, ti);
                     else if (nch_ == 5) ok2 = ilp_chunks(std::integral_constant<int, 5>{}, nch_, row, ti);
                     else if (nch_ == 6) ok2 = ilp_chunks(std::integral_constant<int, 6>{}, nch_, row, ti);
-#else
-                    else if (nch_ <= 5) ok2 = ilp_chunks(std::integral_constant<int, 5>{}, nch_, row, ti);
-#endif
                     else if (nch_ <= 7) ok2 = ilp_chunks(std::integral_constant<int, 7>{}, nch_, row, ti);
                     else if constexpr (XL) {
                         if (nch_ == 8) ok2 = ilp_chunks(std::integral_constant<int, 8>{}, nch_, row, ti);
@@ -1509,7 +1397,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             am_key = 0; am_val = INT_MIN; am_v = 0; am_isend = 0; am_any = false;
             int rc = 0;
             {
-                if (!WPLAN && ((meta >> 16) & 1)) {      // (the wide kernels keep only the general body as fall-back: code size)
+                if (!WIDEB && ((meta >> 16) & 1)) {      // (the wide kernels keep only the general body as fall-back: code size)
                     if (np == 1) rc = fast_body(std::integral_constant<int, 1>{}, row, ti);
                     else if (np == 2) rc = fast_body(std::integral_constant<int, 2>{}, row, ti);
                     else rc = fast_body(std::integral_constant<int, 4>{}, row, ti);
@@ -1546,12 +1434,12 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
     // ---- geometry of the last (partial) tile
     if (status == 0) {
         const int tb = last_done & ~63, rb = tb + lane;
-        if (rb <= last_done) { if (wid == 0) { io.g_bsn[rb] = vg_geo & 0xfff; io.g_esn[rb] = (vg_geo >> 12) & 0xfff; io.g_coff[rb] = (long long)(uint32_t)vg_off * PN; io.row_max_i[rb] = vg_mi; }
+        if (rb <= last_done) { io.g_bsn[rb] = vg_geo & 0xfff; io.g_esn[rb] = (vg_geo >> 12) & 0xfff; io.g_coff[rb] = (long long)(uint32_t)vg_off * PN; io.row_max_i[rb] = vg_mi;
                                if (rb >= 1) n_vec_lane += ((vg_geo >> 12) & 0xfff) - (vg_geo & 0xfff) + 1; }
     }
     WG_SYNC();
     // ---- max_pos_left/right as the reference leaves them (only when the caller reads them back)
-    if (status == 0 && b.want_lr && wid == 0) {
+    if (status == 0 && b.want_lr) {
         const int push_lim = zstop ? last_done : gn;
         for (int r = lane; r < gn; r += 64) {
             int lf = gn, rt = 0;
@@ -1571,7 +1459,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
 
 // The fast path is two kernels -- row loop, then global best + backtrack -- so that the row loop's register allocation
 // (its SGPR budget above all) is not shared with the tail; the hand-over is the AlnOut record in HBM.
-template <typename T, int GAP, int NW = 1, bool WIDEB = false, bool DIR = false, bool XL = false>
+template <typename T, int GAP, bool WIDEB = false, bool DIR = false, bool XL = false>
 __device__ __forceinline__ void align_fast_rows(const DevBatch &b, const AlnDesc &d, AlnOut *out_rec, const int *prog = nullptr) {
     const int lane = threadIdx.x & 63;
     typedef __attribute__((address_space(3))) int lds_int_t;
@@ -1584,21 +1472,21 @@ __device__ __forceinline__ void align_fast_rows(const DevBatch &b, const AlnDesc
     io.planes = (T *)(b.planes + d.plane_off);
     uint8_t *s_query = lds_raw + b.lds.q_off;
     { GLOBAL_AS const uint8_t *g_query = vgpr_ptr(b.query + d.query_off);
-      if constexpr (NW > 1 || WIDEB) {      // two codes to a byte (rows_fast: qat)
-          for (int i = (NW > 1 ? (int)threadIdx.x : lane); 2 * i < d.qlen; i += NW * 64) { const int lo_ = g_query[2 * i], hi_ = 2 * i + 1 < d.qlen ? (int)g_query[2 * i + 1] : 0;
+      if constexpr (WIDEB) {      // two codes to a byte (rows_fast: qat)
+          for (int i = lane; 2 * i < d.qlen; i += 64) { const int lo_ = g_query[2 * i], hi_ = 2 * i + 1 < d.qlen ? (int)g_query[2 * i + 1] : 0;
                   s_query[i] = (uint8_t)((lo_ & 15) | (hi_ << 4)); }
-      } else for (int i = (NW > 1 ? (int)threadIdx.x : lane); i < d.qlen; i += NW * 64) s_query[i] = g_query[i]; }
+      } else for (int i = lane; i < d.qlen; i += 64) s_query[i] = g_query[i]; }
     WG_SYNC();
     long long cursor = 0, n_cells = 0; int status = 0, rows_done = 0, last_done = 0;
     const long long clk0 = (long long)__builtin_amdgcn_s_memtime();
     long long fseg[6] = {0, 0, 0, 0, 0, 0};
     int best3[3] = {d.inf_min, 0, 0};
-    rows_fast<T, GAP, NW, WIDEB, DIR, XL>(b, d, io, s_query, cursor, n_cells, status, rows_done, last_done, fseg, best3);
+    rows_fast<T, GAP, WIDEB, DIR, XL>(b, d, io, s_query, cursor, n_cells, status, rows_done, last_done, fseg, best3);
     const long long clk1 = (long long)__builtin_amdgcn_s_memtime();
 #if !defined(ABPOA_HIP_WIDE_COUNTERS) && !defined(ABPOA_HIP_ROW_CENSUS)
     fseg[5] = (long long)__builtin_amdgcn_s_getreg(63492) | ((long long)__builtin_amdgcn_s_getreg(6164) << 32);      // HW_ID | XCC_ID << 32: where the wave ran (ABPOA_HIP_IMBAL placement report)
 #endif
-    if (NW > 1 ? threadIdx.x == 0 : lane == 0) { GLOBAL_AS AlnOut *o = vgpr_ptr(out_rec); o->status = status; o->n_cells = n_cells; o->cells_used = cursor; o->clk_dp = clk1 - clk0;
+    if (lane == 0) { GLOBAL_AS AlnOut *o = vgpr_ptr(out_rec); o->status = status; o->n_cells = n_cells; o->cells_used = cursor; o->clk_dp = clk1 - clk0;
             o->n_rows_done = rows_done; for (int i_ = 0; i_ < 6; ++i_) o->seg[i_] = fseg[i_];
             if (b.align_mode == ABPOA_HIP_EXTEND_MODE) { o->best_score = best3[0]; o->best_row = best3[1]; o->best_col = best3[2]; } }
     // every way out of the row loop ends the progress word: rows up to last_done are complete, or -1 after a status (backtrack_dir.h SPEC_PROG_*)

@@ -5,8 +5,7 @@
  *                  the largest H of the row; ties go to the lowest lane residue l, then -- inside a lane -- to the end vector (it seeds the
  *                  lane's running maximum), then to the lowest vector.  One unsigned max over the row's keys, one decode to (rowmax, max_i).
  *   carry chain    F of the row is one 64-lane prefix-max scan per chunk of 64 columns; chunk c starts from seed[c] = "first - e" and
- *                  seed[c + 1] = max(total[c], seed[c]) - 64 e, total[c] = max over the chunk's lanes x of hs[x] + x e.  Wavefronts of a team
- *                  start from "nothing" (INT_MIN) and fold the seeds of the wavefronts in front of them in afterwards (carry_fold).
+ *                  seed[c + 1] = max(total[c], seed[c]) - 64 e, total[c] = max over the chunk's lanes x of hs[x] + x e.
  */
 #ifndef ABPOA_WIDE_CLOSED_FORMS_H
 #define ABPOA_WIDE_CLOSED_FORMS_H
@@ -48,13 +47,6 @@ WCF_FN void argmax_decode32(unsigned k, int PN, int beg_sn, int vfloor, int qlen
 
 // ---- carry chain of the F scan: the seed of the next chunk from this chunk's total and seed
 WCF_FN int carry_next(int total, int seed, int e) { return wcf_max(total, seed) - 64 * e; }
-// a seed carried d = (columns) x e further, folded into x: max(x, in - d), saturating -- in = INT_MIN ("nothing") stays below every x
-WCF_FN int carry_fold(int x, int in, int d) { return wcf_max(x, wcf_max(in, INT_MIN + d) - d); }
-// chunks of wavefront w of a team of NW: c0 .. c0 + cnt - 1 (nch / NW each, the first nch % NW one more)
-WCF_FN void team_chunks(int nch, int NW, int w, int &c0, int &cnt) {
-    const int bs = nch / NW, rm = nch - bs * NW;
-    cnt = bs + (w < rm ? 1 : 0); c0 = w * bs + wcf_min(w, rm);
-}
 
 }  // namespace abpoa_hip
 #endif

@@ -104,7 +104,7 @@ static void plan_cases() {
     }
     {   Sets S; S.uniform(1, 30, 500); const abpoa_hip_scoring_t sc = scoring(ABPOA_HIP_AFFINE_GAP, ABPOA_HIP_LOCAL_MODE, 27);
         run_case("local 500 aa", sc, S, 3.0, CONS, false, "g", [](const DevicePlan &P) {
-            CHECK(P.local && P.sc.wb == -1 && !P.general && P.fast_local && P.wide_nw == 0 && P.wide_hi < P.wide_lo && !P.dir && !P.rounds_possible && P.aln_cap == 26); });
+            CHECK(P.local && P.sc.wb == -1 && !P.general && P.fast_local && P.wide_on == 0 && P.wide_hi < P.wide_lo && !P.dir && !P.rounds_possible && P.aln_cap == 26); });
         Sets L; L.uniform(1, 30, 700);
         run_case("local 700 aa", sc, L, 3.0, CONS, false, "dg", [](const DevicePlan &P) { CHECK(P.general && !P.fast_local); });
     }
@@ -132,17 +132,17 @@ static void accessor_cases() {
     CHECK(set_option("ABPOA_HIP_WIDE_LO", "30") == 0 && opt_on("ABPOA_HIP_WIDE_LO") && opt_int("ABPOA_HIP_WIDE_LO", 0) == 30 && set_option("ABPOA_HIP_WIDE_LO", nullptr) == 0);
     // another thread sets and resets a switch while this one reads it: every read sees one snapshot -- unset (the default) or "5"
     std::atomic<bool> stop{false};
-    std::thread flip([&] { for (int i = 0; !stop.load(); ++i) set_option("ABPOA_HIP_TEAM", (i & 1) ? nullptr : "5"); });
+    std::thread flip([&] { for (int i = 0; !stop.load(); ++i) set_option("ABPOA_HIP_RING_ROWS", (i & 1) ? nullptr : "5"); });
     int bad = 0;
-    for (int i = 0; i < 100000; ++i) { const int v = opt_int("ABPOA_HIP_TEAM", -1); (void)opt_on("ABPOA_HIP_TEAM"); if (v != -1 && v != 5) bad++; }
+    for (int i = 0; i < 100000; ++i) { const int v = opt_int("ABPOA_HIP_RING_ROWS", -1); (void)opt_on("ABPOA_HIP_RING_ROWS"); if (v != -1 && v != 5) bad++; }
     stop.store(true); flip.join();
     CHECK(bad == 0);
-    CHECK(set_option("ABPOA_HIP_TEAM", nullptr) == 0 && !opt_set("ABPOA_HIP_TEAM"));
+    CHECK(set_option("ABPOA_HIP_RING_ROWS", nullptr) == 0 && !opt_set("ABPOA_HIP_RING_ROWS"));
 }
 
 int main() {
     // (the harness owns every switch it tests: nothing inherited from the environment)
-    for (const char *sw : {"ABPOA_HIP_NODIR", "ABPOA_HIP_NOWIDE", "ABPOA_HIP_WIDE_LO", "ABPOA_HIP_DEVICE_GENERAL", "ABPOA_HIP_TEAM", "ABPOA_HIP_NOFAST", "ABPOA_HIP_NOXL",
+    for (const char *sw : {"ABPOA_HIP_NODIR", "ABPOA_HIP_NOWIDE", "ABPOA_HIP_WIDE_LO", "ABPOA_HIP_DEVICE_GENERAL", "ABPOA_HIP_NOFAST", "ABPOA_HIP_NOXL",
                            "ABPOA_HIP_RING_ROWS", "ABPOA_HIP_DIR_WIDE", "ABPOA_HIP_EXTRA_ROUTE_MIN", "ABPOA_HIP_ARENA_PCT", "ABPOA_HIP_VERBOSE"}) unsetenv(sw);
     plan_cases();
     accessor_cases();

@@ -32,7 +32,7 @@ def _device_asm(unit, tmp_path_factory):
     return _ASM[unit]
 
 
-@pytest.mark.parametrize("unit", ["poa_rounds", "dp_fast_tail", "dp_wide_rows", "dp_xl_rows", "dp_team_rows"])
+@pytest.mark.parametrize("unit", ["poa_rounds", "dp_fast_tail", "dp_wide_rows", "dp_xl_rows"])
 def test_no_spill_between_async_load_and_wait(unit, tmp_path_factory):
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")

@@ -223,12 +223,12 @@ def test_arena_overflow_retry_keeps_traces(engine, monkeypatch):
     assert n >= 2
 
 
-@pytest.mark.parametrize("env", [{"ABPOA_HIP_RING_ROWS": "4"}, {"ABPOA_HIP_TEAM": "2"}, {"ABPOA_HIP_TEAM": "4"}, {"ABPOA_HIP_NOWIDE": "1"}, {"ABPOA_HIP_DIR_WIDE": "1"},
+@pytest.mark.parametrize("env", [{"ABPOA_HIP_RING_ROWS": "4"}, {"ABPOA_HIP_NOWIDE": "1"}, {"ABPOA_HIP_DIR_WIDE": "1"},
                                  {"ABPOA_HIP_DIR_WIDE": "1", "ABPOA_HIP_RING_ROWS": "4"}],
-                         ids=["ring4_hbm_gather", "team2", "team4", "nowide", "dir_wide", "dir_wide_ring4"])
+                         ids=["ring4_hbm_gather", "nowide", "dir_wide", "dir_wide_ring4"])
 def test_wide_band_variants(engine, monkeypatch, env):
     """The 10 kb goldens (4-5 chunks per row) through the other forms of the wide row loop: a 4-row score ring (every other row gathers a predecessor
-    from the HBM arena), teams of 2 / 4 wavefronts per alignment, the chunk-by-chunk loop of the narrow kernel, and the wide loop with direction words."""
+    from the HBM arena), the chunk-by-chunk loop of the narrow kernel, and the wide loop with direction words."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     n = 0

@@ -1,6 +1,6 @@
 // CPU property checks of abpoa_amd/csrc/wide_closed_forms.h, the integer closed forms of the all-chunks row body (rows_fast.h ilp_chunks), against
 // literal restatements of what they replace.  Built by tests/test_wide_row_closed_forms.py with -fsanitize=undefined (signed overflow aborts).
-//   usage: wide_row_closed_forms key16|key32|carry|team <seed> <iterations>
+//   usage: wide_row_closed_forms key16|key32|carry <seed> <iterations>
 #include <algorithm>
 #include <climits>
 #include <cstdint>
@@ -33,7 +33,7 @@ static void literal_max_in_row(const std::vector<int> &H, int pn, int beg_sn, in
 }
 
 // ---- the arg-max keys: random rows of 1..11 chunks; every in-band lane of every chunk builds its key as ilp_chunks does, the keys are reduced with an
-//      unsigned max in a shuffled order (the DPP reduction, the team's exchange), the winner is decoded and compared with the literal max_in_row
+//      unsigned max in a shuffled order (the DPP reduction), the winner is decoded and compared with the literal max_in_row
 static void check_keys(bool i16, std::mt19937_64 &rng, int iters) {
     const int PN = i16 ? 16 : 8, NV = 64 / PN;
     auto uni = [&](long long lo, long long hi) { return (long long)(lo + (long long)(rng() % (unsigned long long)(hi - lo + 1))); };
@@ -189,45 +189,13 @@ static void check_carry(std::mt19937_64 &rng, int iters) {
     }
 }
 
-// ---- the team fold: the chunks split over NW wavefronts as ilp_chunks splits them; every wavefront runs its own chain from INT_MIN (wavefront 0 from the
-//      row's first column), publishes its last seed, and folds the seeds of the wavefronts in front of it -- equal to the single wavefront's chain
-static void check_team(std::mt19937_64 &rng, int iters) {
-    for (int NW : {2, 4}) for (int pn : {16, 8}) for (int nch = 1; nch <= 11; ++nch) for (int it = 0; it < iters; ++it) {
-        const int e = (int)(rng() % 5);
-        Row r = random_row(rng, pn, nch, e, pn == 16);
-        const std::vector<int> single = seed_chain(r);
-        std::vector<int> out(NW), c0s(NW), cnts(NW);
-        std::vector<std::vector<int>> own(NW);
-        int covered = 0;
-        for (int w = 0; w < NW; ++w) {
-            int c0, cnt; team_chunks(nch, NW, w, c0, cnt); c0s[w] = c0; cnts[w] = cnt;
-            CHECK(c0 == covered && cnt >= 0, "team split nch %d NW %d w %d: c0 %d cnt %d", nch, NW, w, c0, cnt);
-            covered += cnt;
-            std::vector<int> sd(cnt + 1);
-            sd[0] = w == 0 ? (int)r.first - e : INT_MIN;
-            for (int c = 0; c < cnt; ++c) { int s[64], total; chunk_scan(r, c0 + c, s, total); sd[c + 1] = carry_next(total, sd[c], e); }
-            out[w] = sd[cnt]; own[w] = sd;
-        }
-        CHECK(covered == nch, "team split nch %d NW %d covers %d chunks", nch, NW, covered);
-        for (int w = 0; w < NW; ++w) {
-            int in = INT_MIN;
-            for (int j = 0; j < w; ++j) in = carry_fold(out[j], in, cnts[j] * 64 * e);
-            for (int c = 0; c < cnts[w]; ++c) {
-                const int sd = w > 0 ? carry_fold(own[w][c], in, c * 64 * e) : own[w][c];
-                CHECK(sd == single[c0s[w] + c], "team NW %d pn %d nch %d e %d w %d chunk %d: %d, single wavefront %d", NW, pn, nch, e, w, c0s[w] + c, sd, single[c0s[w] + c]);
-            }
-        }
-    }
-}
-
 int main(int argc, char **argv) {
-    if (argc < 4) { printf("usage: %s key16|key32|carry|team <seed> <iterations>\n", argv[0]); return 2; }
+    if (argc < 4) { printf("usage: %s key16|key32|carry <seed> <iterations>\n", argv[0]); return 2; }
     std::mt19937_64 rng(strtoull(argv[2], nullptr, 10));
     const int iters = atoi(argv[3]);
     if (!strcmp(argv[1], "key16")) check_keys(true, rng, iters);
     else if (!strcmp(argv[1], "key32")) check_keys(false, rng, iters);
     else if (!strcmp(argv[1], "carry")) check_carry(rng, iters);
-    else if (!strcmp(argv[1], "team")) check_team(rng, iters);
     else return 2;
     printf("%s: %lld checks, %lld failed\n", argv[1], n_checks, n_fails);
     if (!n_fails) printf("closed forms ok\n");
