@@ -316,6 +316,88 @@ def golden_cases(with_planes_only=False):
     return out
 
 
+_INPUT_KEYS = ("m", "mat", "max_mat", "min_mis", "gap_open1", "gap_ext1", "gap_open2", "gap_ext2", "align_mode", "gap_mode", "wb", "wf", "zdrop", "ret_cigar",
+               "rev_cigar", "n_rows", "qlen", "query", "row_base", "row_node_id", "row_remain", "row_active", "pred_off", "pred_row", "out_off", "out_row",
+               "left_in", "right_in")
+
+
+def first_golden(name):
+    """The first per-alignment container of golden directory `name`, parsed."""
+    return read_abpg([p for label, p in golden_cases() if label.startswith(name + "/")][0])
+
+
+def rescored(g, point, wb=None, wf=None):
+    """A copy of golden container g's input section (graph, query, modes, band state) with the scoring of `point` (tests/scoring_points.py) and,
+    where given, another band: what FlatCase takes.  The golden's alphabet must be the point's."""
+    d = {k: np.array(g[k], copy=True) for k in _INPUT_KEYS}
+    f = point.fields()
+    assert int(d["m"][0]) == int(f["m"][0]), "re-scoring keeps the alphabet"
+    d.update(f)
+    if wb is not None:
+        d["wb"] = np.array([wb], np.int32)
+    if wf is not None:
+        d["wf"] = np.array([wf], np.float32)
+    return d
+
+
+def wrap_regime_rows(case, o):
+    """Share of the active rows (with predecessors) of oracle output `o` (with trace) of `case` that have an in-band column j where the best diagonal
+    predecessor score -- the maximum over the row's predecessors of H[pred][j-1], `inf` standing in where a predecessor's stored range does not cover
+    j-1 -- plus mat[base][query[j-1]] lies below fast_lo = lo + max(oe1, oe2) + PN * max(e1, e2), lo the lowest value of the score width and PN its
+    lanes per vector (16 / 8): the wrap guards of the fast row loops must fire on such a row.  Sufficient, not necessary: E terms can fire them too."""
+    sc = case.sc
+    lo, pn = (-(1 << 15), 16) if o.bits == 16 else (-(1 << 31), 8)
+    fast_lo = lo + max(sc.gap_open1 + sc.gap_ext1, sc.gap_open2 + sc.gap_ext2) + pn * max(sc.gap_ext1, sc.gap_ext2)
+    mat = case.mat.reshape(sc.m, sc.m).astype(np.int64)
+    q = case.query.astype(np.int64)
+
+    def h_row(r):          # (first stored column, H over the stored range)
+        w = (int(o.dp_end_sn[r]) - int(o.dp_beg_sn[r]) + 1) * pn
+        return int(o.dp_beg_sn[r]) * pn, o.planes[int(o.row_off[r]):int(o.row_off[r]) + w].astype(np.int64)
+    n_rows = n_in = 0
+    for r in range(1, case.n_rows):
+        preds = case.pred_row[case.pred_off[r]:case.pred_off[r + 1]]
+        if not o.active[r] or len(preds) == 0:
+            continue
+        n_rows += 1
+        a, b = max(int(o.dp_beg[r]), 1), min(int(o.dp_end[r]), case.qlen)
+        if b < a:
+            continue
+        best = np.full(b - a + 1, o.inf_min, np.int64)          # column j - 1 for j in [a, b]
+        for p in preds:
+            if not o.active[p]:
+                continue
+            c0, h = h_row(int(p))
+            x, y = max(a - 1, c0), min(b - 1, c0 + len(h) - 1)
+            if y >= x:
+                best[x - (a - 1):y - (a - 1) + 1] = np.maximum(best[x - (a - 1):y - (a - 1) + 1], h[x - c0:y - c0 + 1])
+        n_in += bool((best + mat[int(case.row_base[r]), q[a - 1:b]] < fast_lo).any())
+    return n_in / max(n_rows, 1)
+
+
+def key_window_rows(case, o):
+    """Share of the active rows of oracle output `o` (int32, with trace) whose maximum lies outside the window the int32 arg-max key of the wide row loop can
+    hold: floor < maximum < floor + 2^21 - 1 with floor = the first predecessor's row maximum - 2^19 (wide_closed_forms.h).  Such a row is declined."""
+    assert o.bits == 32
+    rmax = {}
+
+    def row_max(r):
+        if r not in rmax:
+            c0, w = int(o.dp_beg_sn[r]) * 8, (int(o.dp_end_sn[r]) - int(o.dp_beg_sn[r]) + 1) * 8
+            h = o.planes[int(o.row_off[r]):int(o.row_off[r]) + w].astype(np.int64)
+            rmax[r] = int(h[int(o.dp_beg[r]) - c0:int(o.dp_end[r]) - c0 + 1].max())
+        return rmax[r]
+    n_rows = n_out = 0
+    for r in range(1, case.n_rows):
+        preds = case.pred_row[case.pred_off[r]:case.pred_off[r + 1]]
+        if not o.active[r] or len(preds) == 0 or not o.active[preds[0]]:
+            continue
+        floor = row_max(int(preds[0])) - (1 << 19)
+        n_rows += 1
+        n_out += not (floor < row_max(r) < floor + (1 << 21) - 1)
+    return n_out / max(n_rows, 1)
+
+
 def run_hip(cases, want_trace=True):
     """Run FlatCases through the C-ABI (abpoa_hip_align_batch); returns a list of OracleOut-like objects."""
     from abpoa_amd import ffi

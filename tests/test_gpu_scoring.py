@@ -1,0 +1,264 @@
+"""GPU (-m gpu): the kernels under the scoring points of tests/scoring_points.py -- asymmetric matrices (every matrix index of the row loops and of the
+backtrack), the wrap guards of the fast row loops on both sides of their threshold, the direction plane at its field caps and just past them, both sides of
+the int16 / int32 gate, the clamps of the int32 arg-max key -- against the C oracle, bit for bit: the small goldens re-scored, at plane level through the flat
+API, without the trace (direction words or score records, the backtrack), and whole read-sets through the device-resident driver against the oracle-backed
+host layer.  tests/test_oracle_vs_reference.py::test_scoring_points pins the oracle to the compiled reference at the same points, and
+tests/test_scoring_regimes.py that the re-scored goldens enter the regimes named here."""
+import ctypes
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import helpers as H
+import scoring_points as SP
+
+pytestmark = pytest.mark.gpu
+NARROW = ["s1k_ag_gb", "s1k_cg_gb", "seq_ag_gb", "heter_cg_gb"]      # global, band of the default width: the direction plane where the penalties allow it
+GB = NARROW + ["ragged_ag_gb"]
+EXT = ["seq_cg_ext", "seq_ag_extz"]
+LOC = ["seq_cg_loc", "ragged_ag_loc"]
+COMP = str.maketrans("ACGTN", "TGCAN")
+
+
+@pytest.fixture(scope="module")
+def engine():
+    from abpoa_amd import ffi
+    lib = ffi.lib()
+    assert lib.abpoa_hip_device_count() >= 1, "no HIP device: the engine has no fallback"
+    ffi.check(lib.abpoa_hip_init(0))
+    return lib
+
+
+_GOLD, _CASES = {}, {}
+
+
+def _case(name, pt, wb=None, wf=None):
+    """(re-scored FlatCase, its input dict, the oracle's output with planes), computed once per module."""
+    k = (name, pt.name, wb, wf)
+    if k not in _CASES:
+        if name not in _GOLD:
+            _GOLD[name] = H.first_golden(name)
+        d = H.rescored(_GOLD[name], pt, wb, wf)
+        c = H.FlatCase(d)
+        _CASES[k] = (c, d, H.run_oracle(c))
+    return _CASES[k]
+
+
+def _dir_counts(lib):
+    out = (ctypes.c_longlong * 2)()
+    lib.abpoa_hip__dir_counts(out)
+    return out[0], out[1]
+
+
+def _both_ways(names, pt, wb=None, wf=None, label=""):
+    """One launch per group of alignments that share every Scoring field: with the trace (bands, every plane cell, row arg-max) and without it (cigar, best
+    cell, result fields, band state) against the oracle."""
+    items = [_case(n, pt, wb, wf) for n in names]
+    for trace in (True, False):
+        outs = H.run_hip([c for c, _, _ in items], want_trace=trace)
+        for n, h, (_, _, o) in zip(names, outs, items):
+            assert hasattr(h, "dp_beg") == trace
+            H.compare_outs(h, o, label=f"{label}{pt.name} {n} wb={wb} trace={trace}")
+
+
+@pytest.mark.parametrize("pt", SP.POINTS, ids=[p.name for p in SP.POINTS])
+def test_every_point_at_plane_level_and_through_the_backtrack(engine, monkeypatch, pt):
+    """Banded global goldens (narrow rows; ragged_ag_gb: rows of a few hundred columns), extension mode with and without z-drop, and the local row loop in
+    both of its forms, re-scored with the point.  Without the trace the backtrack walks direction words exactly where dir_plane_usable holds -- at o1 = 7,
+    o2 = 31, e1 = e2 the saturated fields -- and score records at o1 = 8, o2 = 32, e1 < e2 and under HOXD70."""
+    for grp in (GB, EXT[:1], EXT[1:]):
+        _both_ways(grp, pt)
+    for team in ("0", "1"):
+        monkeypatch.setenv("ABPOA_HIP_LOCAL_TEAM", team)
+        _both_ways(LOC, pt, label=f"local team={team} ")
+    monkeypatch.delenv("ABPOA_HIP_LOCAL_TEAM")
+    _dir_counts(engine)
+    items = [_case(n, pt) for n in NARROW]
+    for h, (_, _, o), n in zip(H.run_hip([c for c, _, _ in items], want_trace=False), items, NARROW):
+        H.compare_outs(h, o, label=f"{pt.name} {n} narrow")
+    walked, redone = _dir_counts(engine)
+    print(f"{pt.name}: direction plane usable {pt.dir_usable()}, walked {walked} of {len(NARROW)}, redone with records {redone}")
+    assert walked == (len(NARROW) if pt.dir_usable() else 0), (pt.name, walked, redone)
+
+
+@pytest.mark.parametrize("pt", SP.group("guard"), ids=[p.name for p in SP.group("guard")])
+def test_guard_pairs_on_bands_of_three(engine, pt):
+    """wb = 3, wf = 0: rows of one or two vectors on which almost every cell borders a cell no score reaches -- the wrap guards hand rows to the exact
+    bodies and the fast path is entered again, row after row (tests/test_scoring_regimes.py: a quarter to three quarters of the rows at the inside points)."""
+    _both_ways(GB, pt, wb=3, wf=0.0)
+    _both_ways(EXT[:1], pt, wb=3, wf=0.0)
+
+
+@pytest.mark.parametrize("pt", SP.group("matrix"), ids=[p.name for p in SP.group("matrix")])
+def test_matrices_on_the_general_kernel(engine, pt):
+    """wb = -1: the unbanded rows of rows_general.h and its two matrix reads, and the record walk of backtrack.h."""
+    _both_ways(["seq_ag_gb", "heter_cg_gb", "ragged_ag_gb"], pt, wb=-1)
+
+
+@pytest.mark.parametrize("pt", SP.group("matrix"), ids=[p.name for p in SP.group("matrix")])
+def test_matrices_on_the_column_slice_windows_of_the_record_walk(engine, monkeypatch, pt):
+    """The record walk of backtrack.h has two copies of its lane-parallel step, each with its own matrix read: over whole-row windows (narrow rows) and over
+    column-slice windows.  Rows of a few hundred columns (ragged_ag_gb through the wide row loop, the 1 kb goldens at wb = 45) with score records
+    (ABPOA_HIP_NODIR=1) and a window of 8 KB take the second."""
+    monkeypatch.setenv("ABPOA_HIP_WIDE_LO", "10")
+    monkeypatch.setenv("ABPOA_HIP_BT_BYTES", "8192")
+    monkeypatch.setenv("ABPOA_HIP_NODIR", "1")
+    _both_ways(["ragged_ag_gb"], pt, label="slices ")
+    _both_ways(["s1k_ag_gb", "s1k_cg_gb"], pt, wb=45, wf=0.0, label="slices ")
+
+
+_DIR_POINTS = ["cap_o7_31", "cap_ag_o7", "cap_e2_2", "guard_dir_x15", "guard_dir_x16"]
+
+
+@pytest.mark.parametrize("name", _DIR_POINTS)
+def test_direction_words_match_the_model_at_the_field_caps(engine, name):
+    """Every direction word the row loops write (trace mode with ABPOA_HIP_DIRTRACE=1) against the words oracle/dir_model.c derives from the oracle's
+    scores: uE == o and dF saturating at cap == o for o1 = 7 and o2 = 31, e1 == e2, and the rows the wrap guard hands to the exact bodies."""
+    pt = SP.BY_NAME[name]
+    assert pt.dir_usable()
+    for n in NARROW:
+        c, d, _ = _case(n, pt)
+        bad = H.dir_words_mismatches(c, d)
+        assert bad is not None and bad == [], (name, n, bad[:5] if bad else bad)
+
+
+@pytest.mark.parametrize("name", ["clamp_m2000000", "clamp_m500000", "asym_cg", "hox_cg"])
+def test_wide_loop_rows_of_two_to_four_chunks(engine, name):
+    """The 1 kb goldens at wb = 45, wf = 0 (rows of 91+ columns).  -M 2000000: most rows' maxima lie at or above the top of the int32 arg-max key's
+    window by the CPU-side criterion (H.key_window_rows, tests/test_scoring_regimes.py), so the all-chunk body has to decline them -- inferred from the inputs,
+    not observed on the device: a row wrongly kept would show as a wrong row arg-max here; -M 500000: every row inside the window.  ASYM5 convex in int16; HOXD70 convex in int32 -- the packed
+    ring word (H - E1) | (H - E2) << 16 with oe2 = 1201."""
+    pt = SP.BY_NAME[name]
+    _both_ways(["s1k_ag_gb", "s1k_cg_gb"], pt, wb=45, wf=0.0)
+    assert _case("s1k_ag_gb", pt, 45, 0.0)[2].bits == (16 if name == "asym_cg" else 32)
+
+
+@pytest.mark.parametrize("name", GB)
+def test_both_sides_of_the_score_width_gate(engine, name):
+    """match = M16 = (32767 - min_mis - oe1 - oe2) // qlen and M16 + 1 under the default penalties: 16 and 32 bits by the oracle's rule, by the engine's
+    Result.bits, and every cell equal -- the 16-bit run with best scores near +32767 (the int16 arg-max key value + 2^15, the packed ring H | E1 << 16)."""
+    g = H.first_golden(name)
+    lib = H.oracle_lib()
+    for pt, bits in zip(SP.width_gate_points(int(g["qlen"][0])), (16, 32)):
+        c, _, o = _case(name, pt)
+        assert lib.abpoa_oracle_score_bits(ctypes.byref(c.sc), c.n_rows, c.qlen, None) == bits and o.bits == bits
+        for trace in (True, False):
+            h = H.run_hip([c], want_trace=trace)[0]
+            assert h.bits == bits, (pt.name, name, h.bits)
+            H.compare_outs(h, o, label=f"{pt.name} {name} trace={trace}")
+        print(f"{pt.name} {name}: {bits} bits, best score {o.best_score}")
+
+
+# ---- whole read-sets through the device-resident driver
+
+def _sets(seed=83, rc=False):
+    """6 sets of 8-14 reads of 150-400 bases, every other one with ragged ends; rc: a third of the reads (never the first) reverse-complemented."""
+    from abpoa_amd import synth
+    rng = np.random.default_rng(seed)
+    sets = []
+    for i, (n, ln) in enumerate(((8, 150), (14, 200), (10, 250), (12, 300), (9, 350), (11, 400))):
+        reads = list(synth.make_read_set(seed, i, n, ln, 0.10))
+        if i % 2:
+            reads = [reads[0]] + [r[int(rng.integers(0, ln // 8)):len(r) - int(rng.integers(0, ln // 8))] for r in reads[1:]]
+        if rc:
+            reads = [(r[::-1].translate(COMP) if j % 3 == 2 else r) for j, r in enumerate(reads)]
+        sets.append(reads)
+    return sets
+
+
+_HOST = {}
+
+
+def _host(pt, amb=False):
+    """The oracle-backed host layer's results for _sets under the point, computed once."""
+    from abpoa_amd import api
+    k = (pt.name, amb)
+    if k not in _HOST:
+        _HOST[k] = api.msa_batch(_sets(rc=amb), pt.params(), out_cons=True, out_msa=True, n_threads=8, lib=H.cpu_shim_lib(), amb_strand=amb)
+    return _HOST[k]
+
+
+def _device_equals_host(pt, amb=False, label=""):
+    from abpoa_amd import api
+    dev = api.msa_batch(_sets(rc=amb), pt.params(), out_cons=True, out_msa=True, n_threads=4, amb_strand=amb)
+    nh = api.msa_timing()["n_host_sets"]
+    if nh:
+        print(f"{label}{pt.name}: {nh} set(s) left the device: {api.host_reasons()}")
+    for i, (a, b) in enumerate(zip(dev, _host(pt, amb))):
+        assert a.status == 0 and b.status == 0, (label, pt.name, i, a.status, b.status)
+        assert a.cons_seq == b.cons_seq and a.cons_cov == b.cons_cov, (label, pt.name, i, "consensus")
+        assert a.msa_seq == b.msa_seq, (label, pt.name, i, "MSA rows")
+        assert a.n_cells == b.n_cells, (label, pt.name, i, a.n_cells, b.n_cells)
+        if amb:
+            assert list(a.is_rc) == list(b.is_rc), (label, pt.name, i, "strand flags")
+    return dev
+
+
+_DRIVER_POINTS = SP.group("matrix") + [p for p in SP.group("guard") if p.inside]
+ASYM_AG_O7 = SP.BY_NAME["asym_ag_o7"]
+
+
+@pytest.mark.parametrize("lockstep", ["0", "1"], ids=["all_rounds_kernel", "lockstep_rounds"])
+@pytest.mark.parametrize("pt", _DRIVER_POINTS, ids=[p.name for p in _DRIVER_POINTS])
+def test_device_driver_equals_the_oracle_backed_host_layer(engine, monkeypatch, pt, lockstep):
+    """Consensus, coverage, MSA rows and cell counts of six read-sets (reads on both sides of HOXD70's and -M 120's width gate) in both forms of the driver."""
+    monkeypatch.setenv("ABPOA_HIP_LOCKSTEP", lockstep)
+    _device_equals_host(pt, label=f"lockstep={lockstep} ")
+
+
+@pytest.mark.parametrize("name", ["asym_cg", "hox_cg"])
+def test_device_driver_strand_retry_under_the_matrices(engine, name):
+    """-s with a third of the reads reverse-complemented: the retry threshold min(qlen, nodes) * max_mat * .3333 with max_mat = 7 and 100, strand flags
+    included."""
+    dev = _device_equals_host(SP.BY_NAME[name], amb=True, label="-s ")
+    assert any(any(r.is_rc) for r in dev)
+
+
+def test_assembly_row_loop_equals_the_compilers_under_an_asymmetric_matrix(engine, monkeypatch):
+    """rows_tight_asm.h reads the extended matrix with its own address arithmetic: ASYM5 affine at o1 = 7 (direction words) with the assembly loop and
+    with the compiler's (ABPOA_HIP_DBG=2048), both against the oracle-backed host layer."""
+    _device_equals_host(ASYM_AG_O7, label="asm ")
+    monkeypatch.setenv("ABPOA_HIP_DBG", "2048")
+    _device_equals_host(ASYM_AG_O7, label="compiler ")
+
+
+_DIGEST_WORKER = r"""
+import ctypes, sys
+sys.path.insert(0, %(root)r); sys.path.insert(0, %(root)r + '/tests')
+import numpy as np
+import helpers as H, scoring_points as SP, test_gpu_scoring as T
+from abpoa_amd import api, ffi, seqio
+def digests(lib, sets, m):
+    lib.abpoa_hip__cigar_digest.restype = ctypes.c_ulonglong
+    out = []
+    for s in sets:
+        a = np.ascontiguousarray(seqio.encode(s[0], m), np.uint8)
+        out.append(int(lib.abpoa_hip__cigar_digest(a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(a), 0)))
+    lib.abpoa_hip__cigar_digest(None, 0, 1)
+    return out
+lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0)); shim = H.cpu_shim_lib()
+sets = T._sets()
+for name in %(names)r:
+    p = SP.BY_NAME[name].params()
+    dev = api.msa_batch(sets, p, n_threads=4); nh = api.msa_timing()['n_host_sets']
+    if nh: print(name, nh, 'set(s) left the device:', api.host_reasons())
+    d_dev = digests(lib, sets, p.m)
+    host = api.msa_batch(sets, p, n_threads=8, lib=shim)
+    d_host = digests(shim, sets, p.m)
+    assert all(r.status == 0 for r in dev) and all(d != 0 for d in d_dev) and d_dev == d_host, (name, d_dev, d_host)
+    assert [r.cons_seq for r in dev] == [r.cons_seq for r in host], name
+    print('CIGARS EQUAL', name)
+"""
+
+
+def test_device_driver_cigars_under_the_matrices(engine):
+    """Every graph cigar of the six sets, folded into a digest per set on the device (ABPOA_HIP_CIGAR_DIGEST=1, read once per process: a child process)
+    and by the oracle-backed host layer: one ASYM5 and one HOXD70 job."""
+    names = ["asym_cg", "hox_cg"]
+    r = subprocess.run([sys.executable, "-c", _DIGEST_WORKER % dict(root=H.ROOT, names=names)], capture_output=True, text=True,
+                       env=dict(os.environ, ABPOA_HIP_CIGAR_DIGEST="1"), timeout=300)
+    print(r.stdout[-2000:])
+    assert r.returncode == 0 and all(f"CIGARS EQUAL {n}" in r.stdout for n in names), (r.stdout[-1500:], r.stderr[-3000:])

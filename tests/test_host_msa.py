@@ -191,3 +191,32 @@ def test_seeded_sweep_of_the_oracle_backed_host_layer_against_the_reference_cli(
         n_ok += 1
     print(f"sweep: {n_ok} outputs identical to abpoa_ref, {n_ref_failed} inputs on which the reference itself fails")
     assert n_ok >= 140 and n_ref_failed <= 20, (n_ok, n_ref_failed)
+
+
+@pytest.mark.skipif(not H.have_ref(), reason="reference build not available")
+def test_scoring_points_sweep_of_the_oracle_backed_host_layer_against_the_reference_cli(tmp_path):
+    """Every point of tests/scoring_points.py (asymmetric matrices, guard pairs, direction-plane caps) x {adaptive band, -b 3 -f 0, -b -1, local, extension,
+    extension with -z 40} x {8 x 120 uncut, 7 x 310 with ragged ends}: the oracle-backed host layer -- what tests/test_gpu_scoring.py compares the
+    device-resident driver with -- prints what the compiled reference prints (`-r 2`), byte for byte."""
+    import numpy as np
+    import scoring_points as SP
+    ref_bin = os.path.join(H.REF_DIR, "abpoa_ref")
+    rng = np.random.default_rng(4242)
+    uncut = list(synth.make_read_set(41, 0, 8, 120, 0.10))
+    ragged = list(synth.make_read_set(41, 1, 7, 310, 0.10))
+    ragged = [ragged[0]] + [r[int(rng.integers(0, 40)):len(r) - int(rng.integers(0, 40))] for r in ragged[1:]]
+    modes = [([], {}), (["-b", "3", "-f", "0"], dict(extra_b=3, extra_f=0.0)), (["-b", "-1"], dict(extra_b=-1)), (["-m", "1"], dict(aln_mode=api.LOCAL)),
+             (["-m", "2"], dict(aln_mode=api.EXTEND)), (["-m", "2", "-z", "40"], dict(aln_mode=api.EXTEND, zdrop=40))]
+    n = 0
+    for si, reads in enumerate((uncut, ragged)):
+        fa = str(tmp_path / f"s{si}.fa")
+        synth.write_fasta(fa, reads)
+        names = [f"r{i}" for i in range(len(reads))]
+        for pt in SP.POINTS:
+            for mo, mk in modes:
+                ref = subprocess.run([ref_bin] + pt.ref_opts() + mo + ["-r", "2", fa], capture_output=True, text=True, timeout=60)
+                assert ref.returncode == 0, (pt.name, mo, si, ref.stderr[-200:])
+                r = api.msa_batch([reads], pt.params(**mk), out_cons=True, out_msa=True, lib=H.cpu_shim_lib(), n_threads=2)[0]
+                assert r.status == 0 and api.format_output(r, names, True, True) == ref.stdout, (pt.name, mo, si)
+                n += 1
+    assert n == 2 * 6 * len(SP.POINTS)

@@ -8,6 +8,7 @@ import os
 import pytest
 
 import helpers as H
+import scoring_points as SP
 from abpoa_amd import synth
 
 pytestmark = pytest.mark.skipif(not H.have_ref(), reason="reference build not available")
@@ -75,3 +76,23 @@ def test_amino_acid_blosum62(tmp_path):
 def test_subgraph(tmp_path):
     _check(tmp_path, "s1", os.path.join(DATA, "seq.fa"), AG, "3,5,8", sub=(10, 40))
     _check(tmp_path, "s2", os.path.join(DATA, "heter.fa"), CG, "4,9", sub=(100, 500))
+
+
+_SCORING_MODES = {"gb": [], "b3": ["-b", "3", "-f", "0"], "b45": ["-b", "45", "-f", "0"], "gu": ["-b", "-1"], "loc": ["-m", "1"], "ext": ["-m", "2"]}
+_SCORING_POINTS = SP.POINTS + SP.CLAMP_POINTS + list(SP.width_gate_points(300))
+
+
+@pytest.fixture(scope="module")
+def scoring_fasta(tmp_path_factory):
+    fa = str(tmp_path_factory.mktemp("scoring") / "s.fa")
+    synth.write_fasta(fa, synth.make_read_set(23, 1, 8, 300, 0.10))
+    return fa
+
+
+@pytest.mark.parametrize("point", _SCORING_POINTS, ids=[p.name for p in _SCORING_POINTS])
+def test_scoring_points(tmp_path, scoring_fasta, point):
+    """The table of tests/scoring_points.py -- asymmetric matrices (ASYM5, HOXD70 as committed), the guard pairs of the fast row loops, the direction
+    plane's field caps, the clamps of the int32 arg-max key, both sides of the int16 / int32 gate -- on 8 x 300 bases in every band (adaptive, 3, 45 -- the wide-loop tests' --, none) / alignment mode: the
+    record behind "the oracle is the reference" for tests/test_gpu_scoring.py, which compares the kernels with the oracle at these points."""
+    for mode, mo in _SCORING_MODES.items():
+        _check(tmp_path, point.name + "_" + mode, scoring_fasta, point.ref_opts() + mo, "all")

@@ -1,6 +1,8 @@
 """Seeded fuzzing of the device-resident driver against the CPU build of the host layer whose aligner is the plain-C oracle (tests/cpu_shim.cpp): random read-set
 shapes (uncut / ragged ends / degenerate), nucleotide or protein, every gap model, alignment mode, band on / off, -s, per-base weights, consensus and MSA.
-Prints the first mismatch with everything needed to replay it and exits 1.  usage: python tools/fuzz_device_vs_oracle.py [--iters N] [--seed S]"""
+With --scoring every nucleotide iteration also takes its matrix and penalties from the table of tests/scoring_points.py (asymmetric matrices, guard pairs,
+direction-plane caps), drawn from a generator of its own: the draws of an iteration's seed are the same with and without the switch.
+Prints the first mismatch with everything needed to replay it and exits 1.  usage: python tools/fuzz_device_vs_oracle.py [--iters N] [--seed S] [--scoring]"""
 import argparse
 import os
 import sys
@@ -42,7 +44,7 @@ def make_sets(rng, seed, aa, small=False):
     return sets
 
 
-def iteration(seed, shim, small=False):
+def iteration(seed, shim, small=False, scoring=False):
     """One seeded option / shape mix on the device-resident driver and on the oracle-backed host run.  Returns (sets on the device, sets through the host
     driver, sets with the same error status on both sides, {reason: sets} of the host-driver sets); raises AssertionError with a replay line on a mismatch."""
     rng = np.random.default_rng(seed)
@@ -63,6 +65,10 @@ def iteration(seed, shim, small=False):
         kw["zdrop"] = int(rng.integers(10, 100))
     if aa:
         kw.update(is_aa=True, score_matrix=workloads.BLOSUM62)
+    elif scoring:      # (a generator of its own: `rng` draws what it draws without the switch)
+        import scoring_points as SP
+        pt = SP.POINTS[int(np.random.default_rng([seed, 0x5C0]).integers(0, len(SP.POINTS)))]
+        kw.update(pt.kw)
     amb = (not aa) and rng.random() < 0.3
     if amb:
         sets = [[(r[::-1].translate(COMP) if (j and rng.random() < 0.3) else r) for j, r in enumerate(s)] for s in sets]
@@ -94,13 +100,14 @@ def iteration(seed, shim, small=False):
 def main():
     ap = argparse.ArgumentParser(); ap.add_argument("--iters", type=int, default=100); ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--small", action="store_true", help="the shapes of the in-suite sweep (reads up to 600 bases, 20 per set)")
+    ap.add_argument("--scoring", action="store_true", help="matrix and penalties of every nucleotide iteration from tests/scoring_points.py")
     a = ap.parse_args()
     lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0))
     shim = H.cpu_shim_lib()
     n_dev = n_host = n_err = 0; hist = {}
     for it in range(a.iters):
         try:
-            d, h, e, why = iteration(a.seed * 100000 + it, shim, a.small)
+            d, h, e, why = iteration(a.seed * 100000 + it, shim, a.small, a.scoring)
         except AssertionError as ex:
             print(ex, flush=True)
             sys.exit(1)
