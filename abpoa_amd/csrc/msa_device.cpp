@@ -399,9 +399,9 @@ void plan_rounds(Job &J) {
     use_rounds = !pl.local && pl.rounds_possible && !dbg_sync && b.lds.wide_on == 0 && !(b.dbg & 64) && pl.max_reads > 2 && !opt_on("ABPOA_HIP_LOCKSTEP");
     b_r = b; rounds_lds = 0;
     if (use_rounds) {
-        // (prepare: 5 bytes per row; fuse: 16 bytes per thread)
+        // (prepare: 5 bytes per row; fuse: static LDS only)
         auto dyn_of = [&](const DevBatch &x) { return std::max<size_t>(std::max<size_t>((size_t)x.lds.total_rows, (size_t)x.lds.total_tail),
-                std::max<size_t>((size_t)5 * (size_t)(p.lds_rows > 0 ? p.lds_rows : 0), (size_t)16 * 256)); };
+                (size_t)5 * (size_t)(p.lds_rows > 0 ? p.lds_rows : 0)); };
         rounds_lds = dyn_of(b_r);
         int st_lds = 0; int nb = poa_rounds_residency(sc->gap_mode, rounds_lds, &st_lds);
         // four workgroups per CU when the job has that many sets: the kernel's static LDS (graph phases) comes out of the backtrack window

@@ -304,10 +304,10 @@ __device__ __forceinline__ void poa_prepare_body(const PoaDev &p, const int s, c
 
 // ---------------------------------------------------------------------------------------------------------------------
 // after the backtrack of round k: fuse the graph cigar of read k into the graph and extend the row order
-// Four wavefronts per read-set; the walk over the query (F2) takes GT positions per pass.
+// Four wavefronts per read-set; the walk over the query (F2) takes 4 GT positions per super-pass.
 __device__ __forceinline__ void poa_fuse_body(const PoaDev &p, const int s, const int k) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    __shared__ int sh_fail, sh_nodes, wtot[GW];
+    __shared__ int wtot[GW];
     const PoaSet S = p.sets[s];
     PoaState *st = p.state + s;
     if (uni(st->status) != POA_ST_OK || k >= S.n_reads) return;
@@ -341,145 +341,276 @@ __device__ __forceinline__ void poa_fuse_body(const PoaDev &p, const int s, cons
         if ((int)(w & 0xf) == ABPOA_HIP_CMATCH) cand[(int)((w >> 4) & 0x3fffffff)] = (int)((w >> 34) & 0x3fffffff);
     }
     __syncthreads();
-    // F2: walk the query in chunks of 64 positions
+    // F2: walk the query in super-passes of FP * GT positions, thread t owning the FP consecutive positions q0 + FP t ...
     int n_nodes = n_old, prev_c = 0 /* source */, prev_new_c = 0, carry_ar = 0 /* row of the source */, carry_sq = -1;
     bool fail = false, fail_slots = false;      // (fail_slots: an edge / aligned list is full -- more node slots would not help, POA_WHY_EDGE_SLOTS)
-    // adds edge from -> to (both lane-private; `from_new` / `to_new`: the node was created by this read, its lists are still empty
-    // apart from what this very walk put there, which is known without a load)
     // per-base weights of this read (-Q), reference :634-667: an edge takes the weight of the base it leads to
     const int32_t *wq = p.wts ? (rc_read ? p.wts_rc : p.wts) + p.read_off[S.read0 + k] : nullptr;
-    auto add_edge = [&](bool act, int from, bool from_new, int to, bool to_new, int w) {
-        if (!act) return;
-        const int64_t F = N0 + from, T = N0 + to;
-        int no = from_new ? 0 : (int)p.nd_nout[F];
-        int hit = -1;
-        if (!from_new && !to_new) for (int t = 0; t < no; ++t) if (out_slot(p, S, F, t) == to) { hit = t; break; }
-        if (hit >= 0) outw_slot(p, S, F, hit) += w;
-        else {
-            const int ni = to_new ? 0 : (int)p.nd_nin[T];
-            // (the source may have any number of out-edges, the sink of in-edges: reads that start / end on different nodes; PoaSet.term0)
-            if (no >= (from == 0 ? imin_(POA_TERM_MAX, p.out_cap + S.n_reads + 2) : p.out_cap) || ni >= (to == 1 ? imin_(POA_TERM_MAX, p.in_cap + S.n_reads + 2) : p.in_cap)) { fail = true;
-                    fail_slots = true; return; }
-            out_slot(p, S, F, no) = to; outw_slot(p, S, F, no) = w; p.nd_nout[F] = (uint8_t)(no + 1);
-            in_slot(p, S, T, ni) = from; p.nd_nin[T] = (uint8_t)(ni + 1);
-            hit = no;
-            // (a new edge: no read went through it yet.  The source's edges beyond the capacity keep no read ids: nothing reads the source's -- the MSA rows
-            //  come from the out-edges of nodes 2.., reference abpoa_output.c:142-150)
-            if (hit < p.out_cap) for (int w_ = 0; w_ < p.rid_words; ++w_) p.nd_rid[(F * p.out_cap + hit) * p.rid_words + w_] = 0;
-        }
-        // read k went through this edge (reference :453-472; a node is the tail of at most one edge per read, so no other lane touches these words)
-        if (p.rid_words && hit < p.out_cap) p.nd_rid[(F * p.out_cap + hit) * p.rid_words + (k >> 6)] |= 1ull << (k & 63);
-        p.nd_nread[F] = (from_new ? 0 : p.nd_nread[F]) + 1;
-    };
-    // all wavefronts walk the query together, GT positions per pass: per-position work (node lookup, new node, edge) is private to
-    // its thread; what flows along the path (new-node ids, previous node, the running maxima AR / sq) crosses wavefronts through LDS
-    __shared__ int sCnt[GW], sMax[GW], sSqm[GW];
-    extern __shared__ int fuse_dyn[];                       // dynamic LDS of the launch (4 * GT ints; in the all-rounds kernel the other phases' space)
-    int *const sNode = fuse_dyn, *const sIsNew = fuse_dyn + GT, *const sAR = fuse_dyn + 2 * GT, *const sSq = fuse_dyn + 3 * GT;
-    for (int q0 = 0; q0 < qlen; q0 += GT) {
-        const int q = q0 + tid; const bool act = q < qlen;
-        const int c = act ? ld_fresh(cand + q) : -1;
-        const int b = act ? (int)seq[q] : 0;
-        int node = -1; bool isnew = act;
-        if (act && c >= 0) {
-            if ((int)p.nd_base[N0 + c] == b) { node = c; isnew = false; }
-            else {                                                              // reference abpoa_get_aligned_id :377-386
-                const int na = p.nd_naln[N0 + c];
-                for (int t = 0; t < na; ++t) { const int a = p.nd_aln[(N0 + c) * p.aln_cap + t]; if ((int)p.nd_base[N0 + a] == b) { node = a; isnew = false; break; } }
-            }
-        }
-        // group-end row of the aligned group that places this position in the row order (see the bookkeeping below); read before
-        // the group is extended
-        int gv = -1;
-        if (act && c >= 0) {
-            const int ref = isnew ? c : node;
-            gv = p.nd_row[N0 + ref];
-            const int na = p.nd_naln[N0 + ref];
-            for (int t = 0; t < na; ++t) gv = imax_(gv, p.nd_row[N0 + p.nd_aln[(N0 + ref) * p.aln_cap + t]]);
-        }
-        // exchange 1: ids of the new nodes (path order) and the running maximum AR
-        const unsigned long long newmask = __ballot(isnew);
-        const int rank = __builtin_popcountll(newmask & ((1ull << lane) - 1));
-        const int gmax_w = wave_scan_max(gv);
-        if (lane == 63) { sCnt[wave] = __builtin_popcountll(newmask); sMax[wave] = gmax_w; }
-        __syncthreads();
-        int before_cnt = 0, n_new = 0, before_max = carry_ar;
+    // (the source may have any number of out-edges, the sink of in-edges: reads that start / end on different nodes; PoaSet.term0)
+    const int out_lim0 = imin_(POA_TERM_MAX, p.out_cap + S.n_reads + 2), in_lim1 = imin_(POA_TERM_MAX, p.in_cap + S.n_reads + 2);
+    // The walk is a chain of dependent gathers (cigar -> node -> aligned group -> its members; edge lists of the previous node), each an L2 / HBM round trip
+    // of ~2 k ticks, so as in poa_prepare_body every load level is issued for all FP positions of a thread before anything waits on the level above, and a
+    // 1 kb read is one super-pass.  Per-position work is private to its thread (the nodes of a path, and their aligned groups, are distinct); what flows
+    // along the path -- new-node ids, the previous node, the running maxima AR / sq -- is handed on inside the thread, then by a wave scan, then through
+    // LDS: two workgroup barriers per super-pass.  A wavefront holds FP * 64 = 256 consecutive positions.
+    constexpr int FP = 4, FA = 3;      // FA: members of an aligned group whose loads are batched (a full A/C/G/T group has three besides the node itself)
+    __shared__ int sCnt[GW], sMax[GW], sSqm[GW], sPrev[2];
+    int *const sLast = wtot;               // (wtot is F4's)
+    for (int q0 = 0; q0 < qlen; q0 += FP * GT) {
+        const int qb = q0 + FP * tid;
+        bool act[FP]; int c[FP], b[FP], cb[FP], na[FP], gv[FP], am[FP][FA], ab[FP][FA], ar[FP][FA];
+        // level 1: the node each position is aligned to, and its base
 #pragma unroll
-        for (int w_ = 0; w_ < GW; ++w_) { const int x_ = sCnt[w_]; n_new += x_; if (w_ < wave) { before_cnt += x_; before_max = imax_(before_max, sMax[w_]); } }
-        if (n_nodes + n_new > S.node_cap) { fail = true; break; }                // (the same in every thread)
-        if (isnew) node = n_nodes + before_cnt + rank;
-        if (isnew) {
-            const int64_t Y = N0 + node;
-            p.nd_base[Y] = (uint8_t)b; p.nd_nin[Y] = 0; p.nd_nout[Y] = 0; p.nd_naln[Y] = 0; p.nd_nread[Y] = 0;
-            if (c >= 0) {                                                       // mismatch: new node joins c's aligned group, reference :393-401
-                const int na = p.nd_naln[N0 + c];
-                if (na + 1 > p.aln_cap) { fail = true; fail_slots = true; }
-                else {
-                    for (int t = 0; t < na; ++t) {
-                        const int other = p.nd_aln[(N0 + c) * p.aln_cap + t];
-                        const int no_ = p.nd_naln[N0 + other];                   // == na for every member of the group
-                        p.nd_aln[(N0 + other) * p.aln_cap + no_] = node; p.nd_naln[N0 + other] = (uint8_t)(no_ + 1);
-                        p.nd_aln[Y * p.aln_cap + t] = other;
-                    }
-                    p.nd_aln[(N0 + c) * p.aln_cap + na] = node; p.nd_naln[N0 + c] = (uint8_t)(na + 1);
-                    p.nd_aln[Y * p.aln_cap + na] = c; p.nd_naln[Y] = (uint8_t)(na + 1);
+        for (int j = 0; j < FP; ++j) { act[j] = qb + j < qlen; c[j] = act[j] ? ld_fresh(cand + qb + j) : -1; b[j] = act[j] ? (int)seq[qb + j] : 0; }
+        // level 2: that node's base, group size and row (positions without a node read the source's: no branch between the loads)
+        bool any_grp = false;
+#pragma unroll
+        for (int j = 0; j < FP; ++j) {
+            const bool h = c[j] >= 0; const int64_t X = N0 + (h ? c[j] : 0);
+            cb[j] = p.nd_base[X]; na[j] = h ? (int)p.nd_naln[X] : 0; gv[j] = h ? p.nd_row[X] : -1;
+            any_grp |= na[j] > 0;
+        }
+        // levels 3 and 4: the first FA members of its aligned group, then their bases and rows
+        if (__any(any_grp)) {
+#pragma unroll
+            for (int j = 0; j < FP; ++j)
+#pragma unroll
+                for (int t = 0; t < FA; ++t) { const bool h = t < na[j]; am[j][t] = p.nd_aln[(N0 + (h ? c[j] : 0)) * p.aln_cap + (h ? t : 0)]; }
+#pragma unroll
+            for (int j = 0; j < FP; ++j)
+#pragma unroll
+                for (int t = 0; t < FA; ++t) { const int64_t X = N0 + (t < na[j] ? am[j][t] : 0); ab[j][t] = p.nd_base[X]; ar[j][t] = p.nd_row[X]; }
+        } else {
+#pragma unroll
+            for (int j = 0; j < FP; ++j)
+#pragma unroll
+                for (int t = 0; t < FA; ++t) { am[j][t] = 0; ab[j][t] = 0; ar[j][t] = 0; }
+        }
+        // the node of every position: the aligned node or the first member of its group with the read's base (reference abpoa_get_aligned_id :377-386),
+        // else a new one.  gv: the group-end row that places the position in the row order (see the bookkeeping below) -- the last row of the aligned
+        // node's group, which is also the group of the member that matched; read before the group is extended.
+        int node[FP]; bool isnew[FP];
+#pragma unroll
+        for (int j = 0; j < FP; ++j) {
+            node[j] = -1; isnew[j] = act[j];
+            if (act[j] && c[j] >= 0) {
+                if (cb[j] == b[j]) { node[j] = c[j]; isnew[j] = false; }
+#pragma unroll
+                for (int t = 0; t < FA; ++t) if (t < na[j]) { if (isnew[j] && ab[j][t] == b[j]) { node[j] = am[j][t]; isnew[j] = false; } gv[j] = imax_(gv[j], ar[j][t]); }
+                for (int t = FA; t < na[j]; ++t) {      // (alphabets with more than four letters)
+                    const int a = p.nd_aln[(N0 + c[j]) * p.aln_cap + t];
+                    if (isnew[j] && (int)p.nd_base[N0 + a] == b[j]) { node[j] = a; isnew[j] = false; }
+                    gv[j] = imax_(gv[j], p.nd_row[N0 + a]);
                 }
             }
         }
+        // exchange 1: new nodes and group-end rows before this thread (ids of the new nodes in path order, running maximum AR), and the last
+        // position of the thread before (an old node's id, -1 for a new node: its id follows from the counts)
+        int cnt = 0, gm = -1;
+#pragma unroll
+        for (int j = 0; j < FP; ++j) { cnt += isnew[j] ? 1 : 0; gm = imax_(gm, gv[j]); }
+        const int icnt = wave_scan_add(cnt), imax = wave_scan_max(gm), lastnode = isnew[FP - 1] ? -1 : node[FP - 1];
+        const int pl = (lane - 1) & 63;
+        const int p_node = shfl(lastnode, pl), p_icnt = shfl(icnt, pl), p_imax = shfl(imax, pl);
+        if (lane == 63) { sCnt[wave] = icnt; sMax[wave] = imax; sLast[wave] = lastnode; }
+        __syncthreads();
+        // The node slots are tested per super-pass; a wavefront's 256 positions are what one pass of the walk used to be, and as then the positions up
+        // to the first 256 that do not fit still put their nodes and edges in (an edge list that is full among them is the reason reported).
+        int before_cnt = 0, n_new = 0, before_max = carry_ar, all_max = carry_ar, wfail = GW;
+#pragma unroll
+        for (int w_ = 0; w_ < GW; ++w_) {
+            const int x_ = sCnt[w_], m_ = sMax[w_];
+            if (w_ < wave) { before_cnt += x_; before_max = imax_(before_max, m_); }
+            n_new += x_; all_max = imax_(all_max, m_);
+            if (wfail == GW && n_nodes + n_new > S.node_cap) wfail = w_;
+        }
+        const bool live = wave < wfail;
         // row-order bookkeeping.  Invariant (the reference's Kahn walk keeps it too, abpoa_graph.c:213-224): the members of an
         // aligned group are contiguous in the row order.  A new node is therefore spliced in right after the END of a group:
         // the group of the node it mismatches (which it joins), or the group of the nearest old node before it on the path,
         // whichever comes later -- i.e. after row AR = running maximum along the path of "group-end row" (old nodes: their own
         // group; mismatch nodes: the group they join; inserted bases: none).  New nodes with the same AR form a run in path order.
-        const int AR = imax_(gmax_w, before_max);
-        // exchange 2: the previous position on the path (thread - 1; thread 0: last position of the previous pass).  The barrier also
-        // orders the new nodes' initialisation above before the edge updates below.
-        sNode[tid] = node; sIsNew[tid] = (int)isnew; sAR[tid] = AR;
-        __syncthreads();
-        const int prev = tid > 0 ? sNode[tid - 1] : prev_c, prev_new = tid > 0 ? sIsNew[tid - 1] : prev_new_c, prevAR = tid > 0 ? sAR[tid - 1] : carry_ar;
-        add_edge(act, prev, prev_new != 0, node, isnew, (wq && act) ? wq[q] : 1);
-        const bool start = isnew && (prev_new == 0 || prevAR != AR);
-        const int sq_w = wave_scan_max(start ? q : -1);
-        if (lane == 63) sSqm[wave] = sq_w;
-        __syncthreads();
-        int sq = imax_(sq_w, carry_sq);
+        int AR[FP], pv[FP]; bool pvn[FP], start[FP];
+        int sqt = -1;
+        {
+            const int ex_cnt = lane ? p_icnt : 0;
+            int run = imax_(before_max, lane ? p_imax : -1), id = n_nodes + before_cnt + ex_cnt;
+            int prv = tid == 0 ? prev_c : (lane ? p_node : sLast[wave ? wave - 1 : 0]);
+            bool prvn = tid == 0 ? prev_new_c != 0 : prv < 0;
+            if (tid != 0 && prvn) prv = id - 1;
 #pragma unroll
-        for (int w_ = 0; w_ < GW; ++w_) if (w_ < wave) sq = imax_(sq, sSqm[w_]);
-        if (isnew) { n_anchor[node - n_old] = AR; n_j[node - n_old] = q - sq + 1; atomicAdd(addcnt + AR, 1); }
-        sSq[tid] = sq;
+            for (int j = 0; j < FP; ++j) {
+                pv[j] = prv; pvn[j] = prvn;
+                const int pAR = run;
+                run = imax_(run, gv[j]); AR[j] = run;
+                if (isnew[j]) node[j] = id++;
+                start[j] = isnew[j] && (!prvn || pAR != run);      // a run of new nodes starts here
+                if (start[j]) sqt = qb + j;
+                prv = node[j]; prvn = isnew[j];
+            }
+        }
+        const int isq = wave_scan_max(sqt), p_isq = shfl(isq, pl);
+        if (lane == 63) sSqm[wave] = isq;
+        {      // carries into the next super-pass: the last position
+            const int qlast = imin_(q0 + FP * GT, qlen) - 1;
+#pragma unroll
+            for (int j = 0; j < FP; ++j) if (qb + j == qlast) { sPrev[0] = node[j]; sPrev[1] = (int)isnew[j]; }
+        }
+        // the new nodes; a mismatch node joins the group of the node it is aligned to, reference :393-401
+#pragma unroll
+        for (int j = 0; j < FP; ++j) if (live && isnew[j]) {
+            const int64_t Y = N0 + node[j], C = N0 + c[j];
+            p.nd_base[Y] = (uint8_t)b[j]; p.nd_nin[Y] = 0; p.nd_nout[Y] = 0; p.nd_naln[Y] = 0; p.nd_nread[Y] = 0;
+            if (c[j] >= 0) {
+                const int na_ = na[j];      // (every member of a group lists all the others: the same count in each)
+                if (na_ + 1 > p.aln_cap) { fail = true; fail_slots = true; }
+                else {
+#pragma unroll
+                    for (int t = 0; t < FA; ++t) if (t < na_) {
+                        const int other = am[j][t];
+                        p.nd_aln[(N0 + other) * p.aln_cap + na_] = node[j]; p.nd_naln[N0 + other] = (uint8_t)(na_ + 1); p.nd_aln[Y * p.aln_cap + t] = other;
+                    }
+                    for (int t = FA; t < na_; ++t) {
+                        const int other = p.nd_aln[C * p.aln_cap + t];
+                        p.nd_aln[(N0 + other) * p.aln_cap + na_] = node[j]; p.nd_naln[N0 + other] = (uint8_t)(na_ + 1); p.nd_aln[Y * p.aln_cap + t] = other;
+                    }
+                    p.nd_aln[C * p.aln_cap + na_] = node[j]; p.nd_naln[C] = (uint8_t)(na_ + 1);
+                    p.nd_aln[Y * p.aln_cap + na_] = c[j]; p.nd_naln[Y] = (uint8_t)(na_ + 1);
+                }
+            }
+        }
+        // the edges previous node -> node (a node created by this read has no edges but the ones this very walk gives it, which is known without a
+        // load): counts, hot out-slots and read count of the old nodes for all FP edges, issued here so that they travel with the stores above
+        bool ea[FP]; int ew[FP], no[FP], ni[FP], nr[FP]; int4 o4[FP];
+#pragma unroll
+        for (int j = 0; j < FP; ++j) {
+            ea[j] = live && act[j];
+            const int64_t F = N0 + ((ea[j] && !pvn[j]) ? pv[j] : 0), T = N0 + ((ea[j] && !isnew[j]) ? node[j] : 0);
+            ew[j] = (wq && act[j]) ? wq[qb + j] : 1;
+            no[j] = p.nd_nout[F]; ni[j] = p.nd_nin[T]; nr[j] = p.nd_nread[F]; o4[j] = *(const int4 *)(p.nd_out + F * POA_HOT);
+        }
+        // exchange 2: where the run of new nodes a position is in began.  The barrier also orders the new nodes' initialisation above before the
+        // edge updates below.
         __syncthreads();
-        // carries into the next pass (from the last active position)
-        const int lt = imin_(GT - 1, qlen - 1 - q0);
-        prev_c = sNode[lt]; prev_new_c = sIsNew[lt]; carry_ar = sAR[lt]; carry_sq = sSq[lt];
-        n_nodes += n_new;
+        int sq = imax_(carry_sq, lane ? p_isq : -1), sq_all = carry_sq;
+#pragma unroll
+        for (int w_ = 0; w_ < GW; ++w_) { const int x_ = sSqm[w_]; sq_all = imax_(sq_all, x_); if (w_ < wave) sq = imax_(sq, x_); }
+#pragma unroll
+        for (int j = 0; j < FP; ++j) {
+            if (start[j]) sq = qb + j;
+            if (live && isnew[j]) { n_anchor[node[j] - n_old] = AR[j]; n_j[node[j] - n_old] = qb + j - sq + 1; atomicAdd(addcnt + AR[j], 1); }
+        }
+        // the edges: which exist (the cold slots only for a node with more than POA_HOT out-edges), then their weights, then the new ones
+        int hit[FP], ow[FP]; int32_t *wp[FP];
+#pragma unroll
+        for (int j = 0; j < FP; ++j) {
+            if (pvn[j]) { no[j] = 0; nr[j] = 0; }
+            if (isnew[j]) ni[j] = 0;
+            hit[j] = -1;
+            if (ea[j] && !pvn[j] && !isnew[j]) {
+                const int to = node[j];
+                if (no[j] > 0 && o4[j].x == to) hit[j] = 0;
+                else if (no[j] > 1 && o4[j].y == to) hit[j] = 1;
+                else if (no[j] > 2 && o4[j].z == to) hit[j] = 2;
+                else if (no[j] > 3 && o4[j].w == to) hit[j] = 3;
+                else for (int t = POA_HOT; t < no[j]; ++t) if (out_slot(p, S, N0 + pv[j], t) == to) { hit[j] = t; break; }
+            }
+            wp[j] = hit[j] >= 0 ? &outw_slot(p, S, N0 + pv[j], hit[j]) : p.nd_outw + N0 * POA_HOT;
+        }
+#pragma unroll
+        for (int j = 0; j < FP; ++j) ow[j] = *wp[j];
+#pragma unroll
+        for (int j = 0; j < FP; ++j) if (ea[j]) {
+            const int from = pv[j], to = node[j];
+            const int64_t F = N0 + from, T = N0 + to;
+            if (hit[j] >= 0) *wp[j] = ow[j] + ew[j];
+            else {
+                if (no[j] >= (from == 0 ? out_lim0 : p.out_cap) || ni[j] >= (to == 1 ? in_lim1 : p.in_cap)) { fail = true; fail_slots = true; continue; }
+                out_slot(p, S, F, no[j]) = to; outw_slot(p, S, F, no[j]) = ew[j]; p.nd_nout[F] = (uint8_t)(no[j] + 1);
+                in_slot(p, S, T, ni[j]) = from; p.nd_nin[T] = (uint8_t)(ni[j] + 1);
+                hit[j] = no[j];
+                // (a new edge: no read went through it yet.  The source's edges beyond the capacity keep no read ids: nothing reads the source's -- the MSA rows
+                //  come from the out-edges of nodes 2.., reference abpoa_output.c:142-150)
+                if (hit[j] < p.out_cap) for (int w_ = 0; w_ < p.rid_words; ++w_) p.nd_rid[(F * p.out_cap + hit[j]) * p.rid_words + w_] = 0;
+            }
+            // read k went through this edge (reference :453-472; a node is the tail of at most one edge per read, so no other lane touches these words)
+            if (p.rid_words && hit[j] < p.out_cap) p.nd_rid[(F * p.out_cap + hit[j]) * p.rid_words + (k >> 6)] |= 1ull << (k & 63);
+            p.nd_nread[F] = nr[j] + 1;
+        }
+        if (wfail < GW) { fail = true; break; }                                  // (the same in every thread)
+        prev_c = sPrev[0]; prev_new_c = sPrev[1]; carry_ar = all_max; carry_sq = sq_all; n_nodes += n_new;
     }
-    // F3: last node -> sink (reference :667)
+    // F3: last node -> sink (reference :667: the last base's weight), on thread 0.  Nothing in the walk touched the last node's out-list or the
+    // sink's in-list, so their loads are issued ahead of the barrier that waits for the walk's stores.
+    int f3_no = 0, f3_ni = 0, f3_nr = 0; int4 f3_o4 = make_int4(0, 0, 0, 0);
+    if (tid == 0) {
+        const int64_t F = N0 + (prev_new_c ? 0 : prev_c);
+        f3_no = p.nd_nout[F]; f3_ni = p.nd_nin[N0 + 1]; f3_nr = p.nd_nread[F]; f3_o4 = *(const int4 *)(p.nd_out + F * POA_HOT);
+    }
     bool any_fail = __syncthreads_or(fail);
-    if (!any_fail) { add_edge(tid == 0, prev_c, prev_new_c != 0, 1, false, wq ? wq[qlen - 1] : 1); any_fail = __syncthreads_or(fail); }      // reference :667: the last base's weight
+    if (!any_fail) {
+        if (tid == 0) {
+            const int from = prev_c, w = wq ? wq[qlen - 1] : 1;
+            const bool from_new = prev_new_c != 0;
+            const int64_t F = N0 + from, T = N0 + 1;
+            const int no = from_new ? 0 : f3_no, ni = f3_ni;
+            int hit = -1;
+            if (no > 0 && f3_o4.x == 1) hit = 0;
+            else if (no > 1 && f3_o4.y == 1) hit = 1;
+            else if (no > 2 && f3_o4.z == 1) hit = 2;
+            else if (no > 3 && f3_o4.w == 1) hit = 3;
+            else for (int t = POA_HOT; t < no; ++t) if (out_slot(p, S, F, t) == 1) { hit = t; break; }
+            bool ok = true;
+            if (hit >= 0) outw_slot(p, S, F, hit) += w;
+            else if (no >= (from == 0 ? out_lim0 : p.out_cap) || ni >= in_lim1) { fail = true; fail_slots = true; ok = false; }
+            else {
+                out_slot(p, S, F, no) = 1; outw_slot(p, S, F, no) = w; p.nd_nout[F] = (uint8_t)(no + 1);
+                in_slot(p, S, T, ni) = from; p.nd_nin[T] = (uint8_t)(ni + 1);
+                hit = no;
+                if (hit < p.out_cap) for (int w_ = 0; w_ < p.rid_words; ++w_) p.nd_rid[(F * p.out_cap + hit) * p.rid_words + w_] = 0;
+            }
+            if (ok) {
+                if (p.rid_words && hit < p.out_cap) p.nd_rid[(F * p.out_cap + hit) * p.rid_words + (k >> 6)] |= 1ull << (k & 63);
+                p.nd_nread[F] = (from_new ? 0 : f3_nr) + 1;
+            }
+        }
+        any_fail = __syncthreads_or(fail);
+    }
     const bool any_slots = __syncthreads_or(fail_slots);
-    if (tid == 0) { sh_fail = any_fail ? (any_slots ? POA_WHY_EDGE_SLOTS : POA_WHY_NODES_IN_FUSE) : POA_WHY_NONE; sh_nodes = n_nodes; }
-    __syncthreads();
-    if (sh_fail) { if (tid == 0) { st->status = POA_ST_FALLBACK; st->reason = sh_fail; } return; }
-    n_nodes = sh_nodes;
-    // F4: new row order = old order with every run of new nodes spliced in after its anchor
+    if (any_fail) { if (tid == 0) { st->status = POA_ST_FALLBACK; st->reason = any_slots ? POA_WHY_EDGE_SLOTS : POA_WHY_NODES_IN_FUSE; } return; }
+    // F4: new row order = old order with every run of new nodes spliced in after its anchor.  FR consecutive rows per thread, their counts and nodes
+    // loaded before the scan: one workgroup scan per FR * GT rows (the graph of a 1 kb read-set: one or two).  The anchors of the first GT new nodes
+    // are loaded ahead of it: they wait for nothing F4 writes.
+    constexpr int FR = 8;
+    const int n_add = n_nodes - n_old;
+    int pl_ar = 0, pl_j = 0;
+    if (tid < n_add) { pl_ar = ld_fresh(n_anchor + tid); pl_j = ld_fresh(n_j + tid); }
     int carry = 0;
-    for (int t0 = 0; t0 < n_old; t0 += GT) {
-        const int r = t0 + tid;
-        const int cnt = r < n_old ? ld_fresh(addcnt + r) : 0;
-        const int incl = wave_scan_add(cnt);
+    for (int r0 = 0; r0 < n_old; r0 += FR * GT) {
+        const int rb = r0 + FR * tid;
+        int cn[FR], u[FR], tot = 0;
+#pragma unroll
+        for (int j = 0; j < FR; ++j) { const bool ok = rb + j < n_old; cn[j] = ok ? ld_fresh(addcnt + rb + j) : 0; u[j] = order_old[ok ? rb + j : 0]; }
+#pragma unroll
+        for (int j = 0; j < FR; ++j) tot += cn[j];
+        const int incl = wave_scan_add(tot);
         if (lane == 63) wtot[wave] = incl;
         __syncthreads();
         int before = 0, all = 0;
 #pragma unroll
         for (int w_ = 0; w_ < GW; ++w_) { const int x_ = wtot[w_]; all += x_; before += w_ < wave ? x_ : 0; }
-        const int shift = carry + before + incl - cnt;      // new nodes anchored at earlier rows
-        if (r < n_old) { const int u = order_old[r]; order_new[r + shift] = u; p.nd_row[N0 + u] = r + shift; addcnt[r] = shift; }
+        int shift = carry + before + incl - tot;            // new nodes anchored at earlier rows
+#pragma unroll
+        for (int j = 0; j < FR; ++j) {
+            const int r = rb + j;
+            if (r < n_old) { order_new[r + shift] = u[j]; p.nd_row[N0 + u[j]] = r + shift; addcnt[r] = shift; }
+            shift += cn[j];
+        }
         carry += all;
         __syncthreads();
     }
-    __syncthreads();
-    for (int i = tid; i < n_nodes - n_old; i += GT) {
-        const int ar = ld_fresh(n_anchor + i), j = ld_fresh(n_j + i);
+    for (int i = tid; i < n_add; i += GT) {
+        const int ar = i < GT ? pl_ar : ld_fresh(n_anchor + i), j = i < GT ? pl_j : ld_fresh(n_j + i);
         const int nr = ar + ld_fresh(addcnt + ar) + j;
         order_new[nr] = n_old + i; p.nd_row[N0 + n_old + i] = nr;
     }

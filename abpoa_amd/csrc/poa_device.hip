@@ -611,7 +611,7 @@ hipError_t launch_poa_prepare(const PoaDev &p, hipStream_t s) {
 }
 hipError_t launch_poa_fuse(const PoaDev &p, hipStream_t s) {
     if (p.n_sets <= 0) return hipSuccess;
-    hipLaunchKernelGGL(poa_fuse_kernel, dim3(p.n_sets), dim3(GT), (size_t)16 * GT, s, p);      // (path-exchange records of the fuse body: 4 ints per thread)
+    hipLaunchKernelGGL(poa_fuse_kernel, dim3(p.n_sets), dim3(GT), 0, s, p);      // (the fuse body's exchanges fit its static LDS)
     return hipGetLastError();
 }
 hipError_t launch_poa_strand_check(const PoaDev &p, hipStream_t s) {
