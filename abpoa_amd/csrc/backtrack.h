@@ -215,11 +215,7 @@ __device__ __forceinline__ void finish_alignment(const DevBatch &b, const AlnDes
             if (n_cigar == 0 || op != ABPOA_HIP_CINS || op != (int)(last_word & 0xf)) {
                 if (n_cigar >= cap) { status = ABPOA_HIP_EBACKTRACK; return; }
                 if (n_cigar > 0 && (n_cigar & 63) == 0) flush_cigar(n_cigar - 64, 64);      // the previous 64 words are final now
-                uint64_t n_id = (uint64_t)(int64_t)node_id, q_id = (uint64_t)(int64_t)query_id, wv;
-                if (op == ABPOA_HIP_CMATCH) wv = n_id << 34 | q_id << 4 | (uint64_t)op;
-                else if (op == ABPOA_HIP_CINS) wv = q_id << 34 | L << 4 | (uint64_t)op;
-                else wv = n_id << 34 | L << 4 | (uint64_t)op;
-                last_word = wv; ++n_cigar;
+                last_word = cigar_word(op, len, node_id, query_id); ++n_cigar;
             } else last_word += L << 4;
             const int w_lo = sgpr((int)(last_word & 0xffffffffull)), w_hi = sgpr((int)(last_word >> 32)), w_idx = sgpr((n_cigar - 1) & 63);
             asm volatile("s_mov_b32 m0, %4\n\ts_nop 3\n\tv_writelane_b32 %0, %2, m0\n\tv_writelane_b32 %1, %3, m0"
@@ -247,10 +243,6 @@ __device__ __forceinline__ void finish_alignment(const DevBatch &b, const AlnDes
 
         int i = best_i, j = best_j, start_i = best_i, start_j = best_j, cur_op = OP_ALL, indel_first = 1;
         if (best_j < qlen) push(ABPOA_HIP_CINS, qlen - j, -1, qlen - 1);
-        // ---- lane-parallel step (cell-record arenas, i.e. the fast path): one LDS round trip each for (a) the row's own record,
-        //      (b) its predecessor list, (c) the predecessors' geometry, (d) every score the decision can need -- lane k holds
-        //      predecessor k -- then the reference's priority order (:109-429) is evaluated on ballot masks.  Falls through to
-        //      the one-read-at-a-time walk below whenever a predecessor is outside the staged window or the row has > 64 of them.
         bool bt_walk_narrow = true;                                // false once a window had to be staged as column slices
         // the walk's state is the same in every lane; values that came out of vector loads (best cell, the one-read-at-a-time step) are
         // moved to SGPRs so that the step loops below run on scalar branches
@@ -270,7 +262,10 @@ __device__ __forceinline__ void finish_alignment(const DevBatch &b, const AlnDes
         //      ballot masks and the chosen predecessor's record becomes the current one.  Falls through to ONE step of the
         //      one-read-at-a-time walk below whenever a predecessor is outside the staged window or the row has > 64 of them.
         int4 cr = make_int4(0, 0, 0, 0); int cr2 = 0, cr_row = -1;               // rinfo / rinfo2 of row cr_row
-        // two copies of the step loop: whole-row windows (narrow bands: no slice bookkeeping at all) and column-slice windows
+        // two copies of the step loop: whole-row windows (narrow bands: no slice bookkeeping at all) and column-slice windows.  An edit to the step goes into BOTH
+        // (tests/test_gpu_scoring.py drives each under the matrix points).  Merged into one generic lambda with a compile-time flag -- as run_loop in
+        // backtrack_dir.h -- the same source made the match run of the slice copy 6 % slower per step on 10 kb reads, its inner loop instruction for instruction
+        // the same (LOG.md, round 11): they stay written out until a merged form is measured equal
         while (CW > 0 && i > 0 && j > 0 && status == 0 && bt_walk_narrow && !local_done) {
             if (i > bt_hi || i < bt_lo) { load_window_cols(i, j); cr_row = -1; if (!win_narrow) { bt_walk_narrow = false; break; } }
             if (cr_row != i) { cr = uniform4(B.rinfo[i - bt_lo]); cr_row = i; }

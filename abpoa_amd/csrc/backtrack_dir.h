@@ -316,10 +316,7 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
             const uint64_t L = (uint64_t)(int64_t)len;
             if (n_cigar == 0 || op != ABPOA_HIP_CINS || op != (int)(last_word & 0xf)) {
                 if (have_pending) store_word(n_cigar - 1, last_word);
-                const uint64_t n_id = (uint64_t)(int64_t)node_row, q_id = (uint64_t)(int64_t)query_id;
-                if (op == ABPOA_HIP_CMATCH) last_word = n_id << 34 | q_id << 4 | (uint64_t)op;
-                else if (op == ABPOA_HIP_CINS) last_word = q_id << 34 | L << 4 | (uint64_t)op;
-                else last_word = n_id << 34 | L << 4 | (uint64_t)op;
+                last_word = cigar_word(op, len, node_row, query_id);
                 have_pending = true; ++n_cigar;
             } else last_word += L << 4;
         };

@@ -295,6 +295,15 @@ __device__ __forceinline__ int4 uniform4(int4 v) {
 }
 __device__ __forceinline__ int2 uniform2(int2 v) { return make_int2(__builtin_amdgcn_readfirstlane(v.x), __builtin_amdgcn_readfirstlane(v.y)); }
 
+// a new 64-bit cigar word (reference abpoa_align.h:54-73): match = node << 34 | query index << 4 | op, insertion = query index << 34 | length << 4 | op,
+// deletion = node << 34 | length << 4 | op.  (An insertion that continues the last word adds its length << 4 to it: the callers do that, each in its own buffering.)
+__device__ __forceinline__ uint64_t cigar_word(int op, int len, int node_id, int query_id) {
+    const uint64_t L = (uint64_t)(int64_t)len, n_id = (uint64_t)(int64_t)node_id, q_id = (uint64_t)(int64_t)query_id;
+    if (op == ABPOA_HIP_CMATCH) return n_id << 34 | q_id << 4 | (uint64_t)op;
+    if (op == ABPOA_HIP_CINS) return q_id << 34 | L << 4 | (uint64_t)op;
+    return n_id << 34 | L << 4 | (uint64_t)op;
+}
+
 extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
 // Which row loop an alignment takes (must agree between the two kernels and with engine.cpp's count).

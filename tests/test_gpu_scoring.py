@@ -102,12 +102,38 @@ def test_matrices_on_the_general_kernel(engine, pt):
 def test_matrices_on_the_column_slice_windows_of_the_record_walk(engine, monkeypatch, pt):
     """The record walk of backtrack.h has two copies of its lane-parallel step, each with its own matrix read: over whole-row windows (narrow rows) and over
     column-slice windows.  Rows of a few hundred columns (ragged_ag_gb through the wide row loop, the 1 kb goldens at wb = 45) with score records
-    (ABPOA_HIP_NODIR=1) and a window of 8 KB take the second."""
+    (ABPOA_HIP_NODIR=1) and a window of 8 KB take the second.
+
+    Which copy a walk takes is arithmetic: a window holds whole rows iff at least min(16, rows) of the rows that end at its last row fit into
+    window bytes / record bytes (records: 4 / 8 / 16 bytes for linear / affine / convex gaps in int16, twice that in int32; ABPOA_HIP_BT_BYTES sets the
+    window, the launch plan's own choice is 28 KB or more for a handful of alignments and never below 8 KB).  Counted over the windows that end at each row
+    up to the best one, from the oracle's bands, the lane-parallel step (cell-record arenas; GAP 0 / 1 / 2 = the *_lg / *_ag / *_cg points) is driven
+
+    in its whole-row copy by test_every_point_at_plane_level_and_through_the_backtrack (rows of 32-80 columns, every window whole at 28 KB):
+      global     GAP 0, 1, 2   s1k_ag_gb, s1k_cg_gb, seq_ag_gb where records are kept: with the trace at every point, without it at the points whose
+                               dir_usable() is false (all of hox_* and *_lg among them: linear gaps have no direction plane)
+      extension  GAP 0, 1, 2   seq_cg_ext, seq_ag_extz at every point (extension mode always keeps records)
+      local      GAP 1, 2      seq_cg_loc (rows of 64 columns) at every point; linear gaps in local mode take the general kernel (no cell records)
+    and in its column-slice copy by this test, at 8 KB:
+      global     GAP 1, 2      ragged_ag_gb (rows of 136-160 columns), the 1 kb goldens at wb = 45 (104-128), heter_cg_gb (64-224)
+      global     GAP 0         ragged_ag_gb, heter_cg_gb: linear gaps keep to band half-widths below 40 (19 and 17 here), so only ragged ends or the bubbles
+                               of a heterozygous graph make rows wide enough -- above 128 columns in int16 (asym_lg: 799 of 1007 and 250 of 797 windows),
+                               above 64 in int32 (hox_lg: 919 of 1007 and 535 of 797); wb = 45 under the *_lg points takes the general kernel
+      extension  GAP 0, 1, 2   heter_cg_extz (rows of 200-224 columns: no window holds whole rows but the topmost)
+      local      GAP 1, 2      ragged_ag_loc (rows of 224 columns), seq_cg_loc at the *_cg points (8 rows of 64 columns fit); seq_cg_loc at the *_ag points
+                               fits 16 rows exactly and stays whole-row here
+    Every matrix point runs every line of the list, but not every point is sensitive to the step's matrix read: where the row loop left its match flags the
+    walk follows them and compares no substitution score.  Measured with the index transposed (s_mat[m * qc + bs_]) in one copy at a time (LOG.md, round
+    11): in the slice copy, this test fails under asym_lg, asym_ag_o7 and hox_lg and nothing else in the file does; in the whole-row copy, the plane-level
+    test fails under the same three points, with the driver tests under every asym_* / hox_* point but hox_lg.  Convex gaps on slices are run here but were
+    not shown sensitive to that read."""
     monkeypatch.setenv("ABPOA_HIP_WIDE_LO", "10")
     monkeypatch.setenv("ABPOA_HIP_BT_BYTES", "8192")
     monkeypatch.setenv("ABPOA_HIP_NODIR", "1")
-    _both_ways(["ragged_ag_gb"], pt, label="slices ")
+    _both_ways(["ragged_ag_gb", "heter_cg_gb"], pt, label="slices ")
     _both_ways(["s1k_ag_gb", "s1k_cg_gb"], pt, wb=45, wf=0.0, label="slices ")
+    _both_ways(["heter_cg_extz"], pt, label="slices extension ")
+    _both_ways(LOC, pt, label="slices local ")
 
 
 _DIR_POINTS = ["cap_o7_31", "cap_ag_o7", "cap_e2_2", "guard_dir_x15", "guard_dir_x16"]
