@@ -1,7 +1,7 @@
 // Long-read form of the wide row loop (dp_wide_rows.hip): rows of 8 - 11 chunks of 64 columns in registers at once, over a 704-column score ring -- reads of
 // 20 - 32 kb (band half-width w = 10 + 0.01 L up to 343; reference src/abpoa_align.h:34-35, src/simd_abpoa_align.c:445).  Until round 5 such rows fell to the
-// chunk-by-chunk bodies (23 k instead of 4 k cycles a row: VERDICT round 4 "missing" 4).  The body is rows_fast.h's ilp_chunks with NCH = 9 / 11 (and 3 / 5 / 7
-// for the narrower rows of the same alignment); it needs up to ~350 VGPRs, so these kernels run one wavefront per SIMD (512 registers) -- which is also what the
+// chunk-by-chunk bodies (23 k instead of 4 k cycles a row: VERDICT round 4 "missing" 4).  The body is rows_fast.h's ilp_chunks with NCH = 8 / 9 / 11 (and 3 .. 7,
+// one per chunk count from 4 on, for the narrower rows of the same alignment); it needs up to ~350 VGPRs, so these kernels run one wavefront per SIMD (512 registers) -- which is also what the
 // LDS allows: a 704-column ring of four rows + 16 KB of packed query is ~28 KB a workgroup.  One kernel per gap model and arena format serves both score widths.
 #include <stdio.h>
 #include <stdlib.h>

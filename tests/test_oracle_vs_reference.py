@@ -9,6 +9,7 @@ import pytest
 
 import helpers as H
 import scoring_points as SP
+import wide_bands as WB
 from abpoa_amd import synth
 
 pytestmark = pytest.mark.skipif(not H.have_ref(), reason="reference build not available")
@@ -96,3 +97,24 @@ def test_scoring_points(tmp_path, scoring_fasta, point):
     record behind "the oracle is the reference" for tests/test_gpu_scoring.py, which compares the kernels with the oracle at these points."""
     for mode, mo in _SCORING_MODES.items():
         _check(tmp_path, point.name + "_" + mode, scoring_fasta, point.ref_opts() + mo, "all")
+
+
+@pytest.mark.parametrize("wb", [184, 250, 324])
+@pytest.mark.parametrize("golden,bits", WB.COMBOS, ids=[f"{g}_i{b}" for g, b in WB.COMBOS])
+def test_wide_bands_on_short_reads(tmp_path, golden, bits, wb):
+    """Three bands of tests/wide_bands.py (-b 184 / 250 / 324 -f 0: rows of 6-7, 8-9 and 11 chunks of 64 columns) on the read-sets of the 1 kb goldens, affine
+    and convex, at match 2 (16 bits) and at the first 32-bit match score: the oracle that tests/test_gpu_wide_bodies.py compares the all-chunk row bodies with
+    is itself cell for cell the compiled reference at wide bands on short reads."""
+    fa = os.path.join(H.GOLDEN_DIR, golden, "input.fa")
+    pt = WB.point(golden, bits, int(H.first_golden(golden)["qlen"][0]))
+    d = str(tmp_path / "w")
+    H.run_ref_dump(fa, d, pt.ref_opts() + ["-b", str(wb), "-f", "0"], "5,11", planes=1)
+    files = sorted(glob.glob(d + "/*.abpg"))
+    assert len(files) == 2
+    for f in files:
+        g = H.read_abpg(f)
+        assert int(g["bits"][0]) == bits and int(g["wb"][0]) == wb
+        pn = 16 if bits == 16 else 8
+        act = g["dp_beg_sn"] >= 0
+        assert int(((g["dp_end_sn"][act] - g["dp_beg_sn"][act] + 1) * pn).max()) > 6 * 64      # rows of seven chunks and more
+        H.compare_with_golden(H.run_oracle(H.FlatCase(g)), g, label=f"{golden} int{bits} wb={wb} " + os.path.basename(f))
