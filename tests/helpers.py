@@ -340,6 +340,36 @@ def rescored(g, point, wb=None, wf=None):
     return d
 
 
+def requeried(g, qlen, period=None, skips=()):
+    """A copy of golden container g's input section (what FlatCase takes; `g` may itself be the result of `rescored` or of this function) with
+    * the query replaced by np.resize(query[:period or len(query)], qlen) -- the golden's own query cut, or tiled with that period -- and qlen set: any query
+      is a legal local alignment against the graph;
+    * skip edges: for each (every, start, dists) and each row r in range(start, n_rows - 1, every) the predecessors r - k, k in dists, with r - k >= 1,
+      that the row does not have yet, appended behind the row's own; the out-edge CSR is rebuilt to match (a source's new targets behind its own).  Rows
+      stay in topological order, so the result is a legal DP input.
+    row_remain and the band state (left_in / right_in) are left as they are: unbanded local mode (wb < 0) reads neither."""
+    d = {k: np.array(g[k], copy=True) for k in _INPUT_KEYS}
+    q = np.asarray(g["query"], np.uint8)
+    d["query"] = np.resize(q[:period or len(q)], qlen).astype(np.uint8)
+    d["qlen"] = np.array([qlen], np.int32)
+    if skips:
+        n = int(d["n_rows"][0])
+        po, pr = d["pred_off"].astype(np.int64), d["pred_row"]
+        oo, orow = d["out_off"].astype(np.int64), d["out_row"]
+        preds = [list(map(int, pr[po[r]:po[r + 1]])) for r in range(n)]
+        outs = [list(map(int, orow[oo[r]:oo[r + 1]])) for r in range(n)]
+        for every, start, dists in skips:
+            for r in range(start, n - 1, every):
+                for k in dists:
+                    if r - k >= 1 and r - k not in preds[r]:
+                        preds[r].append(r - k)
+                        outs[r - k].append(r)
+        for name, lists in (("pred", preds), ("out", outs)):
+            d[name + "_off"] = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int32)
+            d[name + "_row"] = np.array([x for lst in lists for x in lst], np.int32)
+    return d
+
+
 def wrap_regime_rows(case, o):
     """Share of the active rows (with predecessors) of oracle output `o` (with trace) of `case` that have an in-band column j where the best diagonal
     predecessor score -- the maximum over the row's predecessors of H[pred][j-1], `inf` standing in where a predecessor's stored range does not cover

@@ -99,6 +99,45 @@ def test_scoring_points(tmp_path, scoring_fasta, point):
         _check(tmp_path, point.name + "_" + mode, scoring_fasta, point.ref_opts() + mo, "all")
 
 
+LOCAL_READ_LENGTHS = (63, 64, 191, 192, 319, 320, 575, 576)
+
+
+@pytest.mark.parametrize("gap", ["ag", "cg"])
+@pytest.mark.parametrize("alphabet", ["aa", "nt"])
+def test_local_mode_at_the_chunk_edges(tmp_path, alphabet, gap):
+    """Local mode (-m 1), affine and convex, on amino-acid (BLOSUM62) and nucleotide reads of exactly 63, 64, 191, 192, 319, 320, 575 and 576 residues -- both
+    sides of the body switches of the local row loops and of their hand-over to the general kernel -- against a graph one of whose reads carries a 20-residue
+    insertion, so that later rows have a predecessor more than 16 rows back: the oracle that tests/test_gpu_local_bodies.py compares the kernels with is cell
+    for cell the compiled reference there."""
+    import numpy as np
+    rng = np.random.default_rng(20260 + (alphabet == "aa"))
+    letters = np.array(list(synth.AA if alphabet == "aa" else synth.NT))
+
+    def noisy(codes, rate=0.06):
+        out = codes.copy()
+        hit = rng.random(len(out)) < rate
+        out[hit] = rng.integers(0, len(letters), int(hit.sum()))
+        return out
+    base = rng.integers(0, len(letters), 640)
+    reads = [base, noisy(base), np.concatenate([noisy(base[:40]), rng.integers(0, len(letters), 20), noisy(base[40:])])]
+    reads += [noisy(base[7 * i:7 * i + n]) for i, n in enumerate(LOCAL_READ_LENGTHS)]
+    fa = str(tmp_path / "loc.fa")
+    synth.write_fasta(fa, ["".join(letters[r]) for r in reads])
+    opts = ["-m", "1"] + (AG if gap == "ag" else CG) + (["-c", "-t", os.path.join(DATA, "BLOSUM62.mtx")] if alphabet == "aa" else [])
+    d = str(tmp_path / "loc")
+    H.run_ref_dump(fa, d, opts, "all", planes=1)
+    files = sorted(glob.glob(d + "/*.abpg"))
+    qlens, far = [], 0
+    for f in files:
+        g = H.read_abpg(f)
+        assert int(g["align_mode"][0]) == 1 and int(g["wb"][0]) < 0 and int(g["gap_mode"][0]) == (1 if gap == "ag" else 2) and int(g["bits"][0]) == 16
+        qlens.append(int(g["qlen"][0]))
+        po, pr, n = g["pred_off"], g["pred_row"], int(g["n_rows"][0])
+        far += any(r - int(pr[po[r]:po[r + 1]].min()) > 16 for r in range(1, n - 1)) and qlens[-1] in LOCAL_READ_LENGTHS
+        H.compare_with_golden(H.run_oracle(H.FlatCase(g)), g, label=f"local {alphabet} {gap} " + os.path.basename(f))
+    assert tuple(qlens[-len(LOCAL_READ_LENGTHS):]) == LOCAL_READ_LENGTHS and far == len(LOCAL_READ_LENGTHS)
+
+
 @pytest.mark.parametrize("wb", [184, 250, 324])
 @pytest.mark.parametrize("golden,bits", WB.COMBOS, ids=[f"{g}_i{b}" for g, b in WB.COMBOS])
 def test_wide_bands_on_short_reads(tmp_path, golden, bits, wb):
