@@ -25,6 +25,7 @@
 #include <limits.h>
 #include <type_traits>
 #include "engine.h"
+#include "routing.h"
 #include "../../include/abpoa_hip.h"
 
 namespace abpoa_hip {
@@ -306,25 +307,7 @@ __device__ __forceinline__ uint64_t cigar_word(int op, int len, int node_id, int
 
 extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 
-// Which row loop an alignment takes (must agree between the two kernels and with engine.cpp's count).
-__device__ __forceinline__ bool takes_fast(const DevBatch &b, const AlnDesc &d) {
-    return fast_global_job(b.gap_mode, b.align_mode, b.wb, b.e1) && fast_global_aln(b.gap_mode, d.w, d.pad0) && (d.flags & ALN_FAST_OK) && b.lds.fr_cols > 0 &&
-           d.qlen <= b.lds.q_cap && !(b.dbg & 64);
-}
-
-// ... and among those, the ones whose rows are wide enough for the wide row loop (dp_wide_rows.hip); the rest take the narrow one
-// (AlnDesc.pad0: columns the rows are expected to be wider than 2 w -- the device-resident driver sets it for read-sets whose reads differ much in length;
-//  half of it counts as band half-width for the choice of the row loop, nothing else reads it)
-__device__ __forceinline__ bool takes_wide(const DevBatch &b, const AlnDesc &d) {
-    return takes_wide_band(b.lds, d.w + (d.pad0 >> 1));
-}
-
-// ... and which of the fast alignments write direction words instead of score records (dir_plane.h): dir_mode 1 = the narrow-band ones of the launch,
-// dir_mode 2 = the wide-band ones too.
-// (Measured on MI355X: on 1 kb reads the words cost the row loop 5-8 % and save 36-42 % of the backtrack, a net 8-11 %; on 10 kb reads the all-chunks
-//  row loop loses 18-21 % -- more than the backtrack, a fifth of the time there, gains -- so wide-band alignments keep their records while the record
-//  arenas of the job fit the device; the host picks mode 2 when they do not: an eighth of the arena bytes, twice the read-sets in flight.)
-__device__ __forceinline__ bool takes_dir(const DevBatch &b, const AlnDesc &d) { return b.dir_mode == 2 || (b.dir_mode == 1 && !takes_wide(b, d)); }
+// (which row loop an alignment takes -- takes_fast / takes_wide / takes_local / takes_dir and the kernels' guards: routing.h)
 
 // kernel launch helper shared by the translation units (block = NT threads)
 template <typename K>

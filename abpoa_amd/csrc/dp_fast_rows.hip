@@ -11,6 +11,7 @@ __global__ void __launch_bounds__(64) dp_fast_kernel(const DevBatch b) {
     const int a = blockIdx.x;
     if (a >= b.n) return;
     const AlnDesc d = b.aln[a];
+    // (= !for_narrow_kernel(b, d) of routing.h or the other width's; the width test between its two terms, as the kernel has always been compiled)
     if (!takes_fast(b, d) || (BITS != 0 && d.bits != BITS) || takes_wide(b, d)) return;           // dp_kernel's, the other width's, or the wide row loop's
     if (BITS == 16 || (BITS == 0 && d.bits == 16)) align_fast_rows<int16_t, GAP, false, DIR>(b, d, b.out + a);      // (BITS == 0: both widths in one launch, see dp_wide_rows.hip)
     else align_fast_rows<int32_t, GAP, false, DIR>(b, d, b.out + a);

@@ -9,7 +9,7 @@ __global__ void __launch_bounds__(64) dp_fast_tail_kernel(const DevBatch b) {
     const int a = blockIdx.x;
     if (a >= b.n) return;
     const AlnDesc d = b.aln[a];
-    if (!(takes_fast(b, d) || takes_local(b, d)) || (BITS != 0 && d.bits != BITS)) return;
+    if (!ROUTE_FOR_TAIL_KERNEL(b, d) || (BITS != 0 && d.bits != BITS)) return;
     if (BITS == 16 || (BITS == 0 && d.bits == 16)) align_fast_tail<int16_t, GAP, DIR>(b, d, b.out + a);      // (BITS == 0: both widths in one launch, see dp_wide_rows.hip)
     else align_fast_tail<int32_t, GAP, DIR>(b, d, b.out + a);
 }

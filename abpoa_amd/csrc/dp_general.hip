@@ -13,7 +13,7 @@ __global__ void __launch_bounds__(64) dp_kernel(const DevBatch b) {
     const int a = blockIdx.x;
     if (a >= b.n) return;
     const AlnDesc d = b.aln[a];
-    if ((d.flags & ALN_SKIP) || takes_fast(b, d) || takes_local(b, d)) return;            // nothing to do, or the fast row loops'
+    if (!ROUTE_FOR_GENERAL_KERNEL(b, d)) return;            // nothing to do, or the fast row loops'
     if (d.bits == 16) align_one<int16_t, GAP>(b, d, b.out + a);
     else align_one<int32_t, GAP>(b, d, b.out + a);
 }
@@ -30,6 +30,7 @@ hipError_t launch_dp_general(const DevBatch &b, hipStream_t stream) { return b.n
 
 // The fast path is two kernels -- row loop, then global best + backtrack -- so that the row loop's register allocation
 // (its SGPR budget above all) is not shared with the tail; the hand-over is the AlnOut record in HBM.
+// (the guards below decide which kernels are launched; which alignment each of them takes is routing.h's)
 hipError_t launch_dp_fast(const DevBatch &b, hipStream_t stream, hipEvent_t after_rows) {
     if (b.n <= 0) return hipSuccess;
     hipError_t e = hipSuccess;
@@ -41,7 +42,7 @@ hipError_t launch_dp_fast(const DevBatch &b, hipStream_t stream, hipEvent_t afte
     return e;
 }
 
-// n_fast: how many alignments of the batch take the fast row loop (engine.cpp applies takes_fast() on the host); a kernel
+// n_fast: how many alignments of the batch take a fast row loop (engine.cpp counts routing.h for_tail_kernel on the host); a kernel
 // with nothing to do is not launched.
 hipError_t launch_dp(const DevBatch &b, int n_fast, hipStream_t stream, hipEvent_t after_rows) {
     if (b.n <= 0) return hipSuccess;

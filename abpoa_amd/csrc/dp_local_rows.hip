@@ -12,7 +12,7 @@ __global__ void __launch_bounds__(64) dp_local_kernel(const DevBatch b) {
     const int a = blockIdx.x;
     if (a >= b.n) return;
     const AlnDesc d = b.aln[a];
-    if (!takes_local(b, d)) return;
+    if (!for_local_kernel(b, d)) return;
     typedef int16_t T;
     const int lane = threadIdx.x & 63;
     FastIO<T> io;
@@ -40,7 +40,7 @@ __global__ void __launch_bounds__(64 * LOC_NW) dp_local_team_kernel(const DevBat
     const int a = blockIdx.x;
     if (a >= b.n) return;
     const AlnDesc d = b.aln[a];
-    if (!takes_local(b, d)) return;
+    if (!for_local_kernel(b, d)) return;
     typedef int16_t T;
     const int tid = threadIdx.x;
     FastIO<T> io;

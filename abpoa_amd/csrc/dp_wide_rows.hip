@@ -12,6 +12,7 @@ __global__ void __launch_bounds__(64) dp_wide_kernel(const DevBatch b) {
     const int a = blockIdx.x;
     if (a >= b.n) return;
     const AlnDesc d = b.aln[a];
+    // (= !for_wide_kernel(b, d) of routing.h or the other width's; the width test between its two terms, as the kernel has always been compiled)
     if (!takes_fast(b, d) || (BITS != 0 && d.bits != BITS) || !takes_wide(b, d)) return;
     // BITS == 0: both score widths in one launch.  A job whose graphs outgrow int16 on the way has a few rounds in which some read-sets are still
     // int16 and the others already int32; two launches (one per width) would run one after the other, each with the other's SIMDs idle.
@@ -39,7 +40,7 @@ static hipError_t launch_wide_gap(const DevBatch &b, hipStream_t stream) {
 hipError_t launch_xl_rows(const DevBatch &b, hipStream_t stream);      // dp_xl_rows.hip
 hipError_t launch_wide_rows(const DevBatch &b, hipStream_t stream) {
     if (b.lds.wfr_cols == WIDE_RING_COLS_XL) return launch_xl_rows(b, stream);      // rows wider than 448 columns: the long-read form
-    // (wide-band alignments keep their score records in dir_mode 1 and write direction words in dir_mode 2: dp_common.h takes_dir)
+    // (wide-band alignments keep their score records in dir_mode 1 and write direction words in dir_mode 2: routing.h takes_dir)
     if (b.dir_mode == 2) return b.gap_mode == ABPOA_HIP_AFFINE_GAP ? launch_wide_gap<1, true>(b, stream) : launch_wide_gap<2, true>(b, stream);
     return b.gap_mode == ABPOA_HIP_AFFINE_GAP ? launch_wide_gap<1>(b, stream) : launch_wide_gap<2>(b, stream);
 }

@@ -14,7 +14,7 @@ __global__ void __launch_bounds__(64) dp_xl_kernel(const DevBatch b) {
     const int a = blockIdx.x;
     if (a >= b.n) return;
     const AlnDesc d = b.aln[a];
-    if (!takes_fast(b, d) || !takes_wide(b, d)) return;
+    if (!ROUTE_FOR_WIDE_KERNEL(b, d)) return;
     if (d.bits == 16) align_fast_rows<int16_t, GAP, true, DIR, true>(b, d, b.out + a);
     else align_fast_rows<int32_t, GAP, true, DIR, true>(b, d, b.out + a);
 }

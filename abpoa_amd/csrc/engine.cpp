@@ -16,6 +16,7 @@
 #include <algorithm>
 #include "engine_options.h"
 #include "batch_stream.h"
+#include "routing.h"
 #include "dir_plane.h"
 
 namespace abpoa_hip {
@@ -225,28 +226,25 @@ int BatchStream::run() {
         // (ABPOA_HIP_DIR_WIDE=1: words for the wide-band alignments too -- the device-resident driver does that by itself when the record arenas of a
         //  job do not fit the device; here it is a test switch)
         const bool dir_wide = dir && opt_int("ABPOA_HIP_DIR_WIDE", 0) > 0;
+        set_job_fields(b, *sc); b.dbg = opt_int("ABPOA_HIP_DBG", 0); b.dir_mode = dir ? (dir_wide ? 2 : 1) : 0;      // (what the routing rules read: routing.h)
+        int n_fast = 0;       // alignments of the fast row loops; the general kernel has the rest
         for (size_t t = 0; t < todo.size(); ++t) {
             AlnDesc &d = desc_[todo[t]];
-            // direction-plane arenas for the narrow-band alignments of a dir pass; the wide-band ones keep score records (dp_common.h takes_dir / takes_wide)
+            // direction-plane arenas for the narrow-band alignments of a dir pass; the wide-band ones keep score records (routing.h takes_dir)
             // (an alignment the general kernel will run -- seeded band of the -s retry, a row with more predecessors than a word names, no fast row loop in the
-            //  plan -- stores its planes: the records' estimate, not the words'; host mirror of dp_common.h takes_fast)
-            const int dbg_ = opt_int("ABPOA_HIP_DBG", 0);
-            const bool fast_a = (d.flags & ALN_FAST_OK) && fast_global_job(sc->gap_mode, sc->align_mode, sc->wb, sc->gap_ext1) && fast_global_aln(sc->gap_mode, d.w, d.pad0) &&
-                                b.lds.fr_cols > 0 &&
-                                d.qlen <= b.lds.q_cap && !(dbg_ & 64);
-            const bool dir_a = dir && fast_a && (dir_wide || !takes_wide_band(b.lds, d.w));
+            //  plan -- stores its planes: the records' estimate, not the words')
+            const bool dir_a = takes_fast(b, d) && takes_dir(b, d);
+            n_fast += for_tail_kernel(b, d) ? 1 : 0;
             d.plane_cap = dir_a ? (first_pass ? dir_est_cells_[todo[t]] : dir_full_cells_[todo[t]]) : (first_pass ? est_cells_[todo[t]] : full_cells_[todo[t]]);
             d.plane_off = plane_bytes; plane_bytes += (int64_t)align_up((size_t)d.plane_cap * (d.bits / 8) + 64 * 8 * 4);   // + 64 records of slack (fast loop stores whole 64-lane chunks)
             pass[t] = d;
         }
         if ((rc = planes_.reserve((size_t)plane_bytes))) return rc;
         memcpy(hi + o_desc_, pass.data(), sizeof(AlnDesc) * pass.size());
-        b.o1 = sc->gap_open1; b.e1 = sc->gap_ext1; b.o2 = sc->gap_open2; b.e2 = sc->gap_ext2;
-        b.align_mode = sc->align_mode; b.gap_mode = sc->gap_mode; b.wb = sc->wb; b.zdrop = sc->zdrop; b.ret_cigar = sc->ret_cigar; b.rev_cigar = sc->rev_cigar;
+        b.ret_cigar = sc->ret_cigar; b.rev_cigar = sc->rev_cigar;
         b.want_trace = trace ? 1 : 0; b.fresh_band = fresh ? 1 : 0;
-        b.dir_mode = dir ? (dir_wide ? 2 : 1) : 0; b.row_sdist = di + o_sdist_; b.row_pd = (const uint32_t *)(di + o_pd_);
+        b.row_sdist = di + o_sdist_; b.row_pd = (const uint32_t *)(di + o_pd_);
         b.want_lr = (trace || (flags_ & BS_WANT_BAND_STATE)) ? 1 : 0;
-        b.dbg = opt_int("ABPOA_HIP_DBG", 0);
         b.mat = (const int32_t *)(di + o_mat_); b.aln = (const AlnDesc *)(di + o_desc_); b.out = (AlnOut *)(dout + o_rec_);
         b.query = di + o_query_; b.row_base = di + o_base_; b.row_node_id = (const int32_t *)(di + o_nid_); b.row_remain = (const int32_t *)(di + o_rem_);
         b.row_active = di + o_act_; b.pred_off = (const int32_t *)(di + o_poff_); b.pred_row = (const int32_t *)(di + o_pred_);
@@ -275,11 +273,6 @@ int BatchStream::run() {
             HIP_TRY(hipMemsetAsync(dout + o_esn_ + 4 * d.row0, 0xFF, 4 * (size_t)d.n_rows, stream_), ABPOA_HIP_ELAUNCH);
         }
         HIP_TRY(hipEventRecord(ev_[1], stream_), ABPOA_HIP_ELAUNCH);
-        int n_fast = 0;       // mirrors takes_fast() in dp_kernel.hip
-        if (fast_global_job(sc->gap_mode, sc->align_mode, sc->wb, sc->gap_ext1) && b.lds.fr_cols > 0 && !(b.dbg & 64))
-            for (const AlnDesc &d : pass) n_fast += ((d.flags & ALN_FAST_OK) && d.qlen <= b.lds.q_cap && fast_global_aln(sc->gap_mode, d.w, d.pad0)) ? 1 : 0;
-        if (sc->gap_mode != ABPOA_HIP_LINEAR_GAP && sc->align_mode == ABPOA_HIP_LOCAL_MODE && sc->wb < 0 && b.lds.loc_cols > 0 && !(b.dbg & 64))      // mirrors takes_local() in rows_local.h
-            for (const AlnDesc &d : pass) n_fast += ((d.flags & ALN_FAST_OK) && d.bits == 16 && (d.qlen / 16 + 1) * 16 <= b.lds.loc_cols && d.qlen <= b.lds.q_cap) ? 1 : 0;
         HIP_TRY(launch_dp(b, n_fast, stream_, ev_[4]), ABPOA_HIP_ELAUNCH);
         HIP_TRY(hipEventRecord(ev_[2], stream_), ABPOA_HIP_ELAUNCH);
         // results: records + cigars are adjacent at the start of the output blob; band state / trace arrays on demand

@@ -18,7 +18,7 @@ struct AlnDesc {
     int32_t w;           // band half-width, reference :445
     int32_t cigar_cap;   // entries
     int32_t flags;       // ALN_FAST_OK: every row active and max_pos_left/right start as (n_rows, 0) -> the register-resident row loop may be used
-    int32_t pad0;        // expected extra band columns (device-resident driver, PoaSet.band_extra; 0 elsewhere): dp_common.h takes_wide
+    int32_t pad0;        // expected extra band columns (device-resident driver, PoaSet.band_extra; 0 elsewhere): routing.h route_w
     int64_t query_off;   // into query pool (bytes)
     int64_t row0;        // index of DP row 0 in every per-row pool
     int64_t poff0;       // index of pred_off[0] / out_off[0] in the (n_rows+1)-sized offset pools
@@ -68,7 +68,7 @@ struct LdsPlan {
     // --- wide row loop (one wavefront per alignment, rows_fast<.., WIDEB>): its own score ring [wfr_rows][words][wfr_cols + 4] at w_phase_off + fr_off;
     //     wx_off: end of that ring (relative to w_phase_off); wide_on = 0: not used by this launch
     int32_t wfr_rows, wfr_cols, wx_off, wide_on;
-    int32_t wide_w_lo, wide_w_hi; // an alignment takes the wide loop iff wide_w_lo <= its band half-width w <= wide_w_hi (takes_wide_band below)
+    int32_t wide_w_lo, wide_w_hi; // an alignment takes the wide loop iff wide_w_lo <= its band half-width w <= wide_w_hi (routing.h takes_wide_band)
     int32_t narrow_off;           // 1: every alignment of the launch takes the wide loop -- the narrow row-loop kernels are not launched
     int32_t total_wide;           // dynamic LDS bytes of the wide row-loop kernel
     // (the wide kernels' own carve-up: query at q_off packed two 4-bit codes to a byte, then the extended matrix at w_mx_off, then -- w_phase_off -- the ring)
@@ -124,18 +124,7 @@ struct DevBatch {
     uint64_t *cigar;             // pool
 };
 
-// Which jobs / alignments the banded global row loops (rows_fast.h) take -- shared by the kernels (dp_common.h takes_fast) and their host mirrors.
-// (linear gaps, round 5: gap extension >= 1 -- the row arg-max is taken before the in-row scan -- and band half-widths of the narrow loop only: LINEAR_FAST_W; the
-//  wide kernels have no linear form; local / band-less linear jobs stay with the general kernel)
-constexpr int LINEAR_FAST_W = 40;      // = LdsPlan.wide_w_lo's default
-__host__ __device__ inline bool fast_global_job(int gap_mode, int align_mode, int wb, int e1) {
-    if (wb < 0) return false;
-    if (gap_mode == ABPOA_HIP_LINEAR_GAP && e1 < 1) return false;
-    return align_mode == ABPOA_HIP_GLOBAL_MODE || align_mode == ABPOA_HIP_EXTEND_MODE;
-}
-__host__ __device__ inline bool fast_global_aln(int gap_mode, int w, int pad0) { return gap_mode != ABPOA_HIP_LINEAR_GAP || w + (pad0 >> 1) < LINEAR_FAST_W; }
-// ... and among those, the band half-widths (with half of a ragged set's extra columns: dp_common.h takes_wide) that take the wide row loop of the launch
-__host__ __device__ inline bool takes_wide_band(const LdsPlan &L, int w) { return L.wide_on >= 1 && w >= L.wide_w_lo && w <= L.wide_w_hi; }
+// (which row loop takes an alignment, and with which arena format: routing.h)
 
 // Values per DP column in an arena of score records: one padded cell record of the fast loops (rows_fast.h FastFmt::CW) = the planes of the general kernel
 // (linear gaps: {H, match flag} in the fast loops, H alone in the general kernel)

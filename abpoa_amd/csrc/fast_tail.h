@@ -2,7 +2,7 @@
 // the hand-over from the row loop is the AlnOut record.  Used by the tail kernels (dp_fast_tail.hip) and by the all-rounds kernel (poa_rounds.hip).
 #pragma once
 #include "rows_fast.h"      // FastFmt (arena record format)
-#include "rows_local.h"    // takes_local
+#include "rows_local.h"
 #include "backtrack.h"
 #include "backtrack_dir.h"
 

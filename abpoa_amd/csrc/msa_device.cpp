@@ -22,6 +22,7 @@
 #include "msa_batch.h"
 #include "msa_device_debug.h"
 #include "msa_device_plan.h"
+#include "routing.h"
 
 namespace abpoa_hip {
 
@@ -320,52 +321,16 @@ void fill_poa_dev(Job &J) {
     p.cons_node = (int32_t *)(dg + L.o_cnode); p.cons_cov = (int32_t *)(dg + L.o_ccov); p.cons_base = dg + L.o_cbase;
 }
 
-// ---- the launch's LDS plan: sized for the widest rows expected, trimmed to the row-loop kernels that can have work (wide_on, narrow_off), and the score
-//      widths the rounds can meet
-int final_lds_plan(const Job &J, DevBatch &b) {
-    const DevicePlan &pl = J.pl; const abpoa_hip_scoring_t *sc = &pl.sc;
-    int32_t inf_dummy; const int max_bits = abpoa_hip_score_bits(sc, pl.max_node_cap, pl.max_qlen, &inf_dummy); const int pn = max_bits == 16 ? 16 : 8;
-    const int64_t width = padded_width(pl.max_qlen, pn);
-    // (the rings hold the widest rows expected -- up to 1024 columns: beyond that the plan has no fast row loop at all, and a few ragged sets must not send
-    //  the whole job to the host driver; theirs overflow on their own)
-    const int64_t est_plain = pl.est_cols(width, pl.w_max, pn), est_ragged = std::min<int64_t>(std::max<int64_t>(est_plain, std::min<int64_t>(1024, width)),
-            est_plain + pl.max_extra);
-    make_lds_plan(sc, pl.max_qlen, max_bits, est_ragged, J.n_sets, &b.lds);
-    // (a ring that wide does not fit -- int32 scores, convex gaps: the plain estimate then, and the ragged sets' rows that outgrow it are theirs alone)
-    if (pl.max_extra > 0 && b.lds.fr_cols == 0) make_lds_plan(sc, pl.max_qlen, max_bits, est_plain, J.n_sets, &b.lds);
-    // (no fast row loop takes anything: dp_common.h takes_fast / rows_local.h takes_local)
-    if (pl.general) { b.lds.wide_on = 0; b.lds.fr_cols = 0; b.lds.loc_cols = 0; }
-    // the local row loop (rows_local.h takes_local): int16 scores, at most loc_cols columns, query codes in LDS; anything else is the general kernel's
-    else if (pl.local) {
-        b.lds.wide_on = 0;
-        if (max_bits != 16 || b.lds.loc_cols <= 0 || (pl.max_qlen / 16 + 1) * 16 > b.lds.loc_cols || pl.max_qlen > b.lds.q_cap) {
-                set_err("local alignment outside the device row loop's range"); return ABPOA_HIP_EINVAL; }
-    }
-    // score widths the rounds can meet (the width grows with graph and read size): launch only the kernels that can have work
-    int min_qlen = pl.max_qlen;
-    for (int s = 0; s < J.n_sets; ++s) for (int r = 1; r < J.sets[s].n_reads; ++r) min_qlen = std::min(min_qlen, J.sets[s].lens[r]);
-    const int min_bits = abpoa_hip_score_bits(sc, 3, min_qlen, &inf_dummy);
-    b.bits_mask = (min_bits == 16 ? 1 : 0) | (max_bits == 32 ? 2 : 0);
-    // which row-loop kernels can have work at all: band half-widths of the reads that get aligned (w = b + f * length)
-    // (band half-widths as dp_common.h takes_wide counts them: with half of a ragged set's extra columns)
-    const int w_min = std::min(sc->wb + (int)(sc->wf * (float)min_qlen), pl.max_extra ? pl.weff_lo : INT_MAX), w_top = std::max(pl.w_max, pl.weff_hi);
-    const bool mixed = pl.max_extra > 0;      // (sets with and without extra columns: both loops may have work whatever the extremes say)
-    if (!mixed && (w_top < b.lds.wide_w_lo || w_min > b.lds.wide_w_hi)) b.lds.wide_on = 0;                       // no read takes the wide loop
-    b.lds.narrow_off = (!mixed && b.lds.wide_on >= 1 && w_min >= b.lds.wide_w_lo && w_top <= b.lds.wide_w_hi) ? 1 : 0;      // every read does
-    return 0;
-}
-
 // ---- stage 6: arguments of the row-loop kernels (b_rc: the -s retry in the general kernel)
 int fill_dev_batch(Job &J, bool *want_general) {
     const DevicePlan &pl = J.pl; Cache &C = *J.C; const Layout &L = J.L; const abpoa_hip_scoring_t *sc = &pl.sc; const PoaDev &p = J.p; DevBatch &b = J.b, &b_rc = J.b_rc;
     uint8_t *di = C.in.dev, *dr = C.rows.dev; const bool gen_io = pl.gen_io(); int rc;
     memset(&b, 0, sizeof(b));
     b.n = J.n_sets; b.m = sc->m;
-    if ((rc = final_lds_plan(J, b))) return rc;
+    if ((rc = final_lds_plan(pl, J.n_sets, J.sets, b))) { set_err("local alignment outside the device row loop's range"); return rc; }
     // caller falls back to the host driver
-    if (!pl.local && !pl.general && (b.lds.fr_cols == 0 || pl.max_qlen > b.lds.q_cap)) { *want_general = true; set_err("band too wide for the fast row loop"); return ABPOA_HIP_EINVAL; }
-    b.o1 = sc->gap_open1; b.e1 = sc->gap_ext1; b.o2 = sc->gap_open2; b.e2 = sc->gap_ext2;
-    b.align_mode = sc->align_mode; b.gap_mode = sc->gap_mode; b.wb = sc->wb; b.zdrop = sc->zdrop; b.ret_cigar = 1; b.rev_cigar = 0;
+    if (!pl.local && !pl.general && !fast_loop_fits(b.lds, pl.max_qlen)) { *want_general = true; set_err("band too wide for the fast row loop"); return ABPOA_HIP_EINVAL; }
+    set_job_fields(b, *sc); b.ret_cigar = 1; b.rev_cigar = 0;
     b.want_trace = 0; b.fresh_band = 1; b.want_lr = 0;
     b.dbg = opt_int("ABPOA_HIP_DBG", 0);      // (diagnostics: bit 7 keeps the row loop's counters in AlnOut.seg)
     b.mat = (const int32_t *)(di + L.o_mat); b.aln = p.aln; b.out = p.out;

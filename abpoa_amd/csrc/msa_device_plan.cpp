@@ -5,6 +5,7 @@
 #include <string.h>
 #include "engine_options.h"
 #include "msa_device_plan.h"
+#include "routing.h"
 
 namespace abpoa_hip {
 
@@ -99,7 +100,7 @@ void make_lds_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max_bits, in
         }
         L.wx_off = L.fr_off + (int)align_up((size_t)L.wfr_rows * fww * (L.wfr_cols + 4) * 4, 16);
         L.total_wide = L.w_phase_off + L.wx_off;
-        if (P == 1) L.wide_on = 0;      // (linear gaps: the narrow loop only -- dp_common.h takes_fast)
+        if (P == 1) L.wide_on = 0;      // (linear gaps: the narrow loop only -- routing.h fast_global_aln)
     }
 }
 
@@ -114,9 +115,9 @@ int estimate_lds(const abpoa_hip_scoring_t *sc, int n_rows, int max_qlen, bool b
     make_lds_plan(sc, max_qlen, mb, band_cols(padded_width(max_qlen, pn), w, pn, banded), n_aln, pl);
     return mb;
 }
-// jobs the fast row loops exist for: banded global / extension (rows_fast.h), local with affine / convex gaps (rows_local.h)
+// jobs the fast row loops exist for: banded global / extension (rows_fast.h), local with affine / convex gaps (rows_local.h; the plan turns the band off)
 bool global_loops_job(const abpoa_hip_scoring_t *sc) { return fast_global_job(sc->gap_mode, sc->align_mode, sc->wb, sc->gap_ext1); }
-bool local_loop_job(const abpoa_hip_scoring_t *sc) { return sc->gap_mode != ABPOA_HIP_LINEAR_GAP && sc->align_mode == ABPOA_HIP_LOCAL_MODE; }
+bool local_job(const abpoa_hip_scoring_t *sc) { return local_loop_job(sc->gap_mode, sc->align_mode, -1); }
 int longest_read(const abpoa_hip_readset_t &S) { int mx = 0; for (int r = 0; r < S.n_reads; ++r) mx = std::max(mx, S.lens[r]); return mx; }
 }  // namespace
 
@@ -130,7 +131,7 @@ bool msa_device_eligible(const abpoa_hip_scoring_t *sc, unsigned flags) {
     if (sc->align_mode == ABPOA_HIP_LOCAL_MODE && opt_on("ABPOA_HIP_NO_DEVICE_LOCAL")) return false;
     // every gap model and alignment mode: the fast row loops where they apply (banded global, short local), the general kernel otherwise (linear gaps,
     // extension mode with or without z-drop, global mode without a band, long local reads).  ABPOA_HIP_NO_DEVICE_GENERAL=1 sends those back to the host driver.
-    const bool fast = global_loops_job(sc) || local_loop_job(sc);
+    const bool fast = global_loops_job(sc) || local_job(sc);
     if (!fast && opt_on("ABPOA_HIP_NO_DEVICE_GENERAL")) return false;
     return true;
 }
@@ -166,14 +167,14 @@ void choose_kernels(DevicePlan &P, int n_sets, const abpoa_hip_readset_t *sets, 
     const abpoa_hip_scoring_t *sc = &P.sc; const bool banded = !(P.local || P.unbanded);
     {   LdsPlan pl; const int mb = estimate_lds(sc, (int)max_cap0, P.max_qlen, banded, n_sets, &pl);
         // (extension mode, round 5: the same banded rows plus the running best cell / z-drop of reference :1018-1026 -- rows_fast.h commit_row)
-        bool fast_global = global_loops_job(sc) && pl.fr_cols > 0 && P.max_qlen <= pl.q_cap;
-        // (linear gaps, round 5: the narrow row loop only -- every alignment of the job must take it, dp_common.h takes_fast: band half-widths below the wide
+        bool fast_global = global_loops_job(sc) && fast_loop_fits(pl, P.max_qlen);
+        // (linear gaps, round 5: the narrow row loop only -- every alignment of the job must take it, routing.h takes_fast: band half-widths below the wide
         //  loop's, no read-set with ragged ends; anything else is the general kernel's as before)
         if (fast_global && sc->gap_mode == ABPOA_HIP_LINEAR_GAP) {
-            if (P.w_max >= LINEAR_FAST_W) fast_global = false;
+            if (!fast_global_aln(sc->gap_mode, P.w_max, 0)) fast_global = false;
             for (int s = 0; s < n_sets && fast_global; ++s) if (msa_device_set_is_ragged(sets[s])) fast_global = false;      // (the `extra` rule below)
         }
-        P.fast_local = local_loop_job(sc) && mb == 16 && pl.loc_cols > 0 && (P.max_qlen / 16 + 1) * 16 <= pl.loc_cols && P.max_qlen <= pl.q_cap;
+        P.fast_local = local_job(sc) && local_loop_fits(pl, mb, P.max_qlen);
         P.general = !(fast_global || P.fast_local);
         if (opt_on("ABPOA_HIP_DEVICE_GENERAL")) P.general = true;      // (tests: the general kernel for every job)
         if (force_general) P.general = true;
@@ -197,7 +198,7 @@ void choose_kernels(DevicePlan &P, int n_sets, const abpoa_hip_readset_t *sets, 
 // Reads of very different lengths (ends cut at different places; a short read against a long graph): the band is anchored at `qlen - remaining length`
 // (reference abpoa_align.h:34-35), which then sits as far from the alignment's path as the lengths differ, and every row is that much wider than 2 w.
 // Such a set gets `extra` columns in its arena and ring estimates, and its alignments take the wide row loop as if half of them were band half-width
-// (AlnDesc.pad0, dp_common.h takes_wide). Lengths within an eighth of the longest read (at least 64 bases; indel noise: a 25 %-error 400-base set spreads 8
+// (AlnDesc.pad0, routing.h route_w). Lengths within an eighth of the longest read (at least 64 bases; indel noise: a 25 %-error 400-base set spreads 8
 //  %) count as equal: the estimates' own slack
 // (3 vectors + 32 columns) covers those.
 // (route: the part of `extra` that counts for the choice of the row loop)
@@ -213,17 +214,16 @@ void ragged_columns(DevicePlan &P, int n_sets, const abpoa_hip_readset_t *sets) 
         P.extra[s] = spread > tol ? std::min((spread + 15) & ~15, 2048) : 0;
         P.max_extra = std::max(P.max_extra, P.extra[s]);
         P.route[s] = P.extra[s] >= route_min ? P.extra[s] : 0;
-        P.weff_lo = std::min(P.weff_lo, sc->wb + (int)(sc->wf * (float)mn) + P.route[s] / 2);
-        P.weff_hi = std::max(P.weff_hi, sc->wb + (int)(sc->wf * (float)mx) + P.route[s] / 2);
+        P.weff_lo = std::min(P.weff_lo, route_w(sc->wb + (int)(sc->wf * (float)mn), P.route[s]));
+        P.weff_hi = std::max(P.weff_hi, route_w(sc->wb + (int)(sc->wf * (float)mx), P.route[s]));
     }
     if (P.weff_hi == 0) { P.weff_lo = 0; }
 }
 
 // the per-set table (poa_device.h PoaSet) with its offsets into the pools, and the pool totals
 void set_table(DevicePlan &P, int n_sets, const abpoa_hip_readset_t *sets) {
-    const abpoa_hip_scoring_t *sc = &P.sc;
     P.ps.assign(n_sets, PoaSet());
-    P.node_tot = P.pred_tot = P.cig_tot = P.scr_tot = P.plane_tot = P.cons_tot = P.term_tot = 0; P.max_node_cap = 0; P.any_wide_set = false;
+    P.node_tot = P.pred_tot = P.cig_tot = P.scr_tot = P.plane_tot = P.cons_tot = P.term_tot = 0; P.max_node_cap = 0;
     int64_t read_i = 0;
     for (int s = 0; s < n_sets; ++s) {
         PoaSet &S = P.ps[s]; memset(&S, 0, sizeof(S));
@@ -244,17 +244,15 @@ void set_table(DevicePlan &P, int n_sets, const abpoa_hip_readset_t *sets) {
         // (fuse: 3 x qlen + nodes; order / rank passes: up to four tables of one int per node)
         S.scratch0 = P.scr_tot; P.scr_tot += 3LL * P.max_qlen + 4 * cap + 8;
         S.cons_cap = (int)std::min<int64_t>(cap, 2LL * mx + 64); S.cons0 = P.cons_tot; P.cons_tot += S.cons_cap;
-        const int w = sc->wb + (int)(sc->wf * (float)mx) + P.route[s] / 2;      // (for the choice of the row loop: dp_common.h takes_wide)
         S.band_extra = P.route[s];
         P.max_node_cap = std::max(P.max_node_cap, (int)cap);
-        P.any_wide_set |= (w >= P.wide_lo && w <= P.wide_hi);
     }
 }
 }  // namespace
 
 // arenas: the widest score type a set can reach decides the cell size; columns per row as the band estimate of engine.cpp
 void DevicePlan::size_arenas(const abpoa_hip_readset_t *sets, bool dw) {
-    plane_tot = 0;
+    plane_tot = 0; set_wide.assign(ps.size(), 0); set_dir.assign(ps.size(), 0); any_wide_set = false;
     const int pct_ = opt_int("ABPOA_HIP_ARENA_PCT", 0);
     for (size_t s = 0; s < ps.size(); ++s) {
         PoaSet &S = ps[s]; const int mx = longest_read(sets[s]);
@@ -279,8 +277,10 @@ void DevicePlan::size_arenas(const abpoa_hip_readset_t *sets, bool dw) {
         // (direction words for every row, score records for the first row and for about one row in four -- rows a successor beyond the score ring or the
         //  global best will read from HBM; half of the rows where the wide loop's ring is only four rows deep; a set that needs more is flagged and
         //  redone like any other capacity miss)
-        const bool wide_s = !local && w + route[s] / 2 >= wide_lo && w + route[s] / 2 <= wide_hi;
-        const bool dir_s = dir && (dw || !wide_s);      // (dp_common.h takes_dir)
+        // (which row loop and which arena format the set's alignments will take: routing.h takes_wide / takes_dir at the set's longest read)
+        const bool wide_s = !local && in_wide_range(wide_lo, wide_hi, route_w(w, route[s]));
+        const bool dir_s = dir_for(dir ? (dw ? 2 : 1) : 0, wide_s);
+        set_wide[s] = wide_s; set_dir[s] = dir_s; any_wide_set |= wide_s;
         const int64_t rec_div = (wide_s && wide_ring_rows <= 4) ? 2 : 4;
         // (bytes per cell record of a row that keeps its scores: CW values -- the wide kernel's compact records: 4 B int16 affine, else 8 B; rows_fast.h
         //  CWR)
@@ -329,6 +329,37 @@ DevicePlan plan_device_job(const abpoa_hip_scoring_t *sc_in, int n_sets, const a
     set_table(P, n_sets, sets);
     P.size_arenas(sets, P.dir_wide);
     return P;
+}
+
+int final_lds_plan(const DevicePlan &pl, int n_sets, const abpoa_hip_readset_t *sets, DevBatch &b) {
+    const abpoa_hip_scoring_t *sc = &pl.sc;
+    int32_t inf_dummy; const int max_bits = abpoa_hip_score_bits(sc, pl.max_node_cap, pl.max_qlen, &inf_dummy); const int pn = max_bits == 16 ? 16 : 8;
+    const int64_t width = padded_width(pl.max_qlen, pn);
+    // (the rings hold the widest rows expected -- up to 1024 columns: beyond that the plan has no fast row loop at all, and a few ragged sets must not send
+    //  the whole job to the host driver; theirs overflow on their own)
+    const int64_t est_plain = pl.est_cols(width, pl.w_max, pn), est_ragged = std::min<int64_t>(std::max<int64_t>(est_plain, std::min<int64_t>(1024, width)),
+            est_plain + pl.max_extra);
+    make_lds_plan(sc, pl.max_qlen, max_bits, est_ragged, n_sets, &b.lds);
+    // (a ring that wide does not fit -- int32 scores, convex gaps: the plain estimate then, and the ragged sets' rows that outgrow it are theirs alone)
+    if (pl.max_extra > 0 && b.lds.fr_cols == 0) make_lds_plan(sc, pl.max_qlen, max_bits, est_plain, n_sets, &b.lds);
+    // (no fast row loop takes anything: routing.h takes_fast / takes_local)
+    if (pl.general) { b.lds.wide_on = 0; b.lds.fr_cols = 0; b.lds.loc_cols = 0; }
+    // the local row loop: anything it does not take is the general kernel's
+    else if (pl.local) {
+        b.lds.wide_on = 0;
+        if (!local_loop_fits(b.lds, max_bits, pl.max_qlen)) return ABPOA_HIP_EINVAL;
+    }
+    // score widths the rounds can meet (the width grows with graph and read size): launch only the kernels that can have work
+    int min_qlen = pl.max_qlen;
+    for (int s = 0; s < n_sets; ++s) for (int r = 1; r < sets[s].n_reads; ++r) min_qlen = std::min(min_qlen, sets[s].lens[r]);
+    const int min_bits = abpoa_hip_score_bits(sc, 3, min_qlen, &inf_dummy);
+    b.bits_mask = (min_bits == 16 ? 1 : 0) | (max_bits == 32 ? 2 : 0);
+    // which row-loop kernels can have work at all: band half-widths of the reads that get aligned (w = b + f * length), as routing.h route_w counts them
+    const int w_min = std::min(sc->wb + (int)(sc->wf * (float)min_qlen), pl.max_extra ? pl.weff_lo : INT_MAX), w_top = std::max(pl.w_max, pl.weff_hi);
+    const bool mixed = pl.max_extra > 0;      // (sets with and without extra columns: both loops may have work whatever the extremes say)
+    if (!mixed && !wide_range_meets(b.lds.wide_w_lo, b.lds.wide_w_hi, w_min, w_top)) b.lds.wide_on = 0;             // no read takes the wide loop
+    b.lds.narrow_off = (!mixed && takes_wide_band(b.lds, w_min) && takes_wide_band(b.lds, w_top)) ? 1 : 0;          // every read does (w_min <= w_top)
+    return 0;
 }
 
 }  // namespace abpoa_hip

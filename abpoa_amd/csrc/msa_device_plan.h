@@ -23,11 +23,14 @@ struct DevicePlan {
     bool roomy; int in_cap, out_cap;      // the last pass of the ladder: an edge slot per read at every node
     // band half-widths that take the wide row loop (LdsPlan.wide_w_lo / hi; none when the wide kernels are off), depth of its score ring.  wide_on / wfr_cols:
     // the wide loop's switch and ring columns of the ESTIMATE the range comes from (0 where the job has no wide loop) -- kept for the CPU test alone; no
-    // driver stage reads them, the launch's final values are DevBatch.lds.wide_on / wfr_cols (msa_device.cpp final_lds_plan)
+    // driver stage reads them, the launch's final values are DevBatch.lds.wide_on / wfr_cols (final_lds_plan)
     int wide_lo, wide_hi, wide_ring_rows, wide_on, wfr_cols;
     // ragged sets: extra columns per set, the part of them that counts for the choice of the row loop, the largest, the effective band half-widths
     std::vector<int> extra, route; int max_extra, weff_lo, weff_hi;
     bool dir_wide, dir_wide_auto, any_wide_set;      // direction words for the wide-band sets too / ABPOA_HIP_DIR_WIDE leaves that to the driver / a set takes the wide loop
+    // per set, what size_arenas assumed of the alignment of its longest read: the wide row loop / direction words (routing.h takes_wide / takes_dir) -- kept for
+    // the CPU test, which holds them against the per-alignment rule; any_wide_set is their summary
+    std::vector<uint8_t> set_wide, set_dir;
     std::vector<PoaSet> ps;
     int64_t node_tot, pred_tot, cig_tot, scr_tot, cons_tot, term_tot, plane_tot; int max_node_cap;
 
@@ -39,6 +42,9 @@ struct DevicePlan {
 };
 
 DevicePlan plan_device_job(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, double node_factor, unsigned flags, bool force_general);
+// the launch's LDS plan (b.lds) and score widths (b.bits_mask): sized for the widest rows expected, trimmed to the row-loop kernels that can have work (wide_on,
+// narrow_off); ABPOA_HIP_EINVAL: a local job outside the local row loop's range
+int final_lds_plan(const DevicePlan &pl, int n_sets, const abpoa_hip_readset_t *sets, DevBatch &b);
 // the wide row loop's workgroups per CU for a job of these sets when all of them take it with one wavefront each; 0: they do not (msa_device_resident_sets)
 int wide_sets_per_cu(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets);
 

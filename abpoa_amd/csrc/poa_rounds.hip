@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(GT, 4) poa_rounds_kernel(const int slot, const
         if ((tid >> 6) == worker) {
             const int bits = b.aln[s].bits, w = b.aln[s].w, flags = b.aln[s].flags;
             // (the host launches this kernel only for jobs whose reads all take the narrow loop)
-            if ((flags & ALN_FAST_OK) && !(b.lds.wide_on >= 1 && w >= b.lds.wide_w_lo && w <= b.lds.wide_w_hi)) {
+            if (ROUTE_ROUNDS_TAKES(b, flags, w)) {
                 bool done_dir = false;
                 if constexpr (GAP != 0) if (b.dir_mode) {      // (linear gaps keep H records: no direction words)
                     int *prog = pair ? sh_walk + 8 * SPEC_WK : nullptr;
@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(GT, 4) poa_rounds_kernel(const int slot, const
         } else if (GAP != 0 && b.dir_mode && pair) {      // the other three wavefronts: helpers of the backtrack (backtrack_dir.h)
             if constexpr (GAP != 0) {
             const int bits = b.aln[s].bits, w = b.aln[s].w, flags = b.aln[s].flags, hr = (((int)(tid >> 6) - worker) & (GW - 1));
-            if ((flags & ALN_FAST_OK) && !(b.lds.wide_on >= 1 && w >= b.lds.wide_w_lo && w <= b.lds.wide_w_hi)) {
+            if (ROUTE_ROUNDS_TAKES(b, flags, w)) {
                 if (bits == 16) rounds_tail<int16_t, GAP, true>(slot, s, hr, sh_walk, k); else rounds_tail<int32_t, GAP, true>(slot, s, hr, sh_walk, k);
             }
             }

@@ -17,12 +17,7 @@
 
 namespace abpoa_hip {
 
-// (alignments this loop takes; must agree between the kernels and the host: engine.cpp)
-__device__ __forceinline__ bool takes_local(const DevBatch &b, const AlnDesc &d) {
-    // (int16 scores only: a local alignment of at most loc_cols columns cannot need more unless the matrix is extreme -- then the general kernel takes it)
-    return b.align_mode == ABPOA_HIP_LOCAL_MODE && b.wb < 0 && b.gap_mode != ABPOA_HIP_LINEAR_GAP && (d.flags & ALN_FAST_OK) && b.lds.loc_cols > 0 && d.bits == 16 &&
-           (d.qlen / 16 + 1) * 16 <= b.lds.loc_cols && d.qlen <= b.lds.q_cap && !(b.dbg & 64);
-}
+// (alignments this loop takes: routing.h takes_local)
 
 template <typename T, int GAP, int NCH>
 __device__ __forceinline__ void rows_local(const DevBatch &b, const AlnDesc &d, const FastIO<T> &io, const uint8_t *s_query, AlnOut *out_rec) {

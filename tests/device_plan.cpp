@@ -2,15 +2,19 @@
 // and the typed switch accessors of engine_options.cpp.  No GPU, no HIP runtime call; built with -fsanitize=undefined,address.
 // The expected routing is what DESIGN.md section 1 and section 4.7 document (w = b + f * length; wide row loop for 40 <= w <= 215 -- 343 in the long-read form
 // --; local row loop up to 575 columns; ragged sets: spread over max(64, longest / 8) becomes extra columns; linear gaps on the narrow loop only ...).
+// Every planned job is also held against the kernels' per-alignment routing rule (abpoa_amd/csrc/routing.h): routing_checks below.
 // Only plan fields that do not depend on lds_fixed_bytes_dp / _bt are asserted: the two values below are stand-ins for the kernels' own.
+#include <algorithm>
 #include <atomic>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <string>
 #include <thread>
 #include <vector>
 #include "engine_options.h"
 #include "msa_device_plan.h"
+#include "routing.h"
 
 // (the snapshot a set_option replaces is left alone on purpose -- engine_options.h -- so the leak check would report every switch this harness flips)
 extern "C" const char *__asan_default_options() { return "detect_leaks=0"; }
@@ -48,13 +52,57 @@ static abpoa_hip_scoring_t scoring(int gap_mode, int align_mode = ABPOA_HIP_GLOB
     return sc;
 }
 
+// The plan's job-level answers against the per-alignment rule of the kernels (routing.h): the launch's DevBatch as msa_device.cpp fill_dev_batch builds it, and
+// for every set and every read length in it the round's AlnDesc as poa_bodies.h poa_prepare_body builds it, at the score widths of the first round (three graph
+// rows) and of the set's node slots.  A job that the driver would hand back to the host (final_lds_plan fails, no fast row loop in the final plan) has no launch.
+// known_e: sets for which (e) is a known disagreement of today's rules (LOG.md); it is asserted as such, so that a fix has to come here
+static int g_routed = 0;
+static void routing_checks(const DevicePlan &P, Sets &S, const std::vector<int> &known_e = {}) {
+    const abpoa_hip_scoring_t *sc = &P.sc;
+    DevBatch b; memset(&b, 0, sizeof(b)); b.n = S.n(); b.m = sc->m;
+    if (final_lds_plan(P, S.n(), S.get(), b)) return;
+    if (!P.local && !P.general && !fast_loop_fits(b.lds, P.max_qlen)) return;
+    set_job_fields(b, *sc); b.dir_mode = P.dir ? (P.dir_wide ? 2 : 1) : 0; b.dbg = 0;
+    CHECK(P.set_wide.size() == P.ps.size() && P.set_dir.size() == P.ps.size());
+    bool all_local = true, any_wide = false;
+    for (int s = 0; s < S.n(); ++s) {
+        int longest = 0; for (int l : S.lens[s]) longest = std::max(longest, l);
+        any_wide |= P.set_wide[s] != 0;
+        for (int qlen : S.lens[s]) for (int n_rows : {3, (int)P.ps[s].node_cap}) {
+            AlnDesc d; memset(&d, 0, sizeof(d));
+            d.n_rows = n_rows; d.qlen = qlen; d.bits = abpoa_hip_score_bits(sc, n_rows, qlen, &d.inf_min);
+            d.w = sc->wb < 0 ? qlen : sc->wb + (int)(sc->wf * (float)qlen);
+            d.flags = P.general ? 0 : ALN_FAST_OK; d.pad0 = P.ps[s].band_extra;
+            const bool nar = for_narrow_kernel(b, d), wid = for_wide_kernel(b, d), loc = for_local_kernel(b, d), gen = for_general_kernel(b, d);
+            CHECK((int)nar + (int)wid + (int)loc + (int)gen == 1);                          // (a)
+            CHECK(for_tail_kernel(b, d) == (nar || wid || loc));
+            CHECK(gen == P.general);                               // (b), (c): no kernel is launched for a general alignment of a fast job
+            all_local &= loc;
+            if (b.lds.narrow_off) CHECK(!nar);                                              // (f)
+            if (b.lds.wide_on == 0) CHECK(!wid);
+            if (P.rounds_possible) CHECK(rounds_takes(b, d.flags, d.w) && nar);             // (g)
+            if (qlen == longest) {                                                        // (e): what size_arenas sized the set's arena for
+                const bool known = std::find(known_e.begin(), known_e.end(), s) != known_e.end();
+                const bool agree = takes_wide(b, d) == (P.set_wide[s] != 0) && takes_dir(b, d) == (P.set_dir[s] != 0);
+                CHECK(agree != known);
+            }
+            d.flags = ALN_SKIP; CHECK(!for_general_kernel(b, d));
+            g_routed++;
+        }
+    }
+    CHECK(P.fast_local == all_local);                                                       // (d)
+    CHECK(P.any_wide_set == any_wide);
+}
+
 // One case: the plan's documented answer, then the same job with one switch set (what: 'd' NODIR -> no direction words, the choice of kernels untouched;
 // 'w' NOWIDE -> empty wide range; 'l' WIDE_LO=30 -> the range starts at 30, for jobs that have a wide loop; 'g' DEVICE_GENERAL -> the general kernel), then
 // the switch reset: the first answer must come back.  Every case names at least one switch.
 template <typename F>
-static void run_case(const char *name, const abpoa_hip_scoring_t &sc, Sets &S, double node_factor, unsigned flags, bool force_general, const char *what, F expect) {
+static void run_case(const char *name, const abpoa_hip_scoring_t &sc, Sets &S, double node_factor, unsigned flags, bool force_general, const char *what, F expect,
+                     const std::vector<int> &known_e = {}) {
     g_case = name;
     const DevicePlan B = plan_device_job(&sc, S.n(), S.get(), node_factor, flags, force_general); expect(B); CHECK((int)B.ps.size() == S.n());
+    routing_checks(B, S, known_e);
     CHECK(*what != 0);
     for (const char *c = what; *c; ++c) {
         g_case = std::string(name) + " + switch " + *c;
@@ -65,9 +113,11 @@ static void run_case(const char *name, const abpoa_hip_scoring_t &sc, Sets &S, d
         if (*c == 'w') CHECK(P.wide_hi < P.wide_lo && !P.any_wide_set && P.general == B.general && P.dir == B.dir);
         if (*c == 'l') CHECK(P.wide_lo == 30);
         if (*c == 'g') CHECK(P.general && !P.dir && !P.fast_local && !P.lin_fast && !P.rounds_possible);
+        routing_checks(P, S, *c == 'g' ? std::vector<int>() : known_e);
         CHECK(set_option(sw, nullptr) == 0);
         g_case = std::string(name) + " after reset of switch " + *c;
         const DevicePlan Q = plan_device_job(&sc, S.n(), S.get(), node_factor, flags, force_general); expect(Q);
+        routing_checks(Q, S, known_e);
     }
 }
 
@@ -111,7 +161,7 @@ static void plan_cases() {
     {   Sets S; S.uniform(3, 3, 1000); S.add({1000, 1000, 600}); S.add({1000, 900}); const abpoa_hip_scoring_t sc = scoring(ABPOA_HIP_AFFINE_GAP);
         run_case("ragged set", sc, S, 3.0, CONS, false, "d", [](const DevicePlan &P) {
             CHECK(!P.general && P.extra[0] == 0 && P.extra[1] == 0 && P.extra[2] == 0 && P.extra[3] == 400 && P.extra[4] == 0 && P.max_extra == 400 && !P.rounds_possible);
-            CHECK(P.ps[3].band_extra == 400 && P.ps[4].band_extra == 0); });
+            CHECK(P.ps[3].band_extra == 400 && P.ps[4].band_extra == 0); }, {3});      // (set 3: the disagreement of "ragged set, routed past 40" below)
     }
     {   Sets S; S.uniform(2, 20, 1000); const abpoa_hip_scoring_t sc = scoring(ABPOA_HIP_AFFINE_GAP);
         run_case("last pass, 20 reads", sc, S, 4096.0, CONS, false, "dwg", [](const DevicePlan &P) { CHECK(P.roomy && P.in_cap == 21 && P.out_cap == 21 && !P.dir && !P.rounds_possible); });
@@ -120,6 +170,44 @@ static void plan_cases() {
         Sets U; U.uniform(1, 400, 1000);
         run_case("last pass, 400 reads", sc, U, 4096.0, CONS, false, "wg", [](const DevicePlan &P) { CHECK(P.in_cap == 250 && P.out_cap == 250 && !P.dir); });
     }
+}
+
+// The edges of the routing rules (-b 10 -f 0.01: w = 10 + length / 100), each through run_case and so through routing_checks
+static void routing_cases() {
+    const unsigned CONS = ABPOA_HIP_OUT_CONS;
+    const abpoa_hip_scoring_t aff = scoring(ABPOA_HIP_AFFINE_GAP), lin = scoring(ABPOA_HIP_LINEAR_GAP);
+    {   Sets A; A.uniform(3, 4, 2900); Sets B; B.uniform(3, 4, 3000);      // the wide loop's first band half-width
+        run_case("w 39", aff, A, 3.0, CONS, false, "dwg", [](const DevicePlan &P) { CHECK(P.w_max == 39 && !P.general && !P.any_wide_set && P.rounds_possible); });
+        run_case("w 40", aff, B, 3.0, CONS, false, "dwlg", [](const DevicePlan &P) { CHECK(P.w_max == 40 && !P.general && P.any_wide_set && !P.rounds_possible); });
+        run_case("linear w 39", lin, A, 3.0, CONS, false, "wg", [](const DevicePlan &P) { CHECK(P.w_max == 39 && !P.general && P.lin_fast && P.rounds_possible); });
+        run_case("linear w 40", lin, B, 3.0, CONS, false, "wg", [](const DevicePlan &P) { CHECK(P.w_max == 40 && P.general && !P.lin_fast); });
+    }
+    {   Sets A; A.uniform(2, 3, 20500); Sets B; B.uniform(2, 3, 20600);      // the last one of the 448-column ring; the long-read form goes on to 343
+        run_case("w 215", aff, A, 3.0, CONS, false, "wg", [](const DevicePlan &P) { CHECK(P.w_max == 215 && !P.general && P.any_wide_set && P.wide_hi == 343); });
+        run_case("w 216", aff, B, 3.0, CONS, false, "wg", [](const DevicePlan &P) { CHECK(P.w_max == 216 && !P.general && P.any_wide_set && P.wide_hi == 343); });
+        CHECK(set_option("ABPOA_HIP_NOXL", "1") == 0);
+        run_case("w 215, no long-read form", aff, A, 3.0, CONS, false, "wg", [](const DevicePlan &P) { CHECK(!P.general && P.any_wide_set && P.wide_hi == 215 && P.wfr_cols == 448); });
+        run_case("w 216, no long-read form", aff, B, 3.0, CONS, false, "wg", [](const DevicePlan &P) { CHECK(!P.general && !P.any_wide_set && P.wide_hi == 215); });
+        CHECK(set_option("ABPOA_HIP_NOXL", nullptr) == 0);
+    }
+    {   const abpoa_hip_scoring_t loc = scoring(ABPOA_HIP_AFFINE_GAP, ABPOA_HIP_LOCAL_MODE, 27);      // the local loop's 576 columns
+        Sets A; A.uniform(2, 5, 575); Sets B; B.uniform(2, 5, 576);
+        run_case("local 575", loc, A, 3.0, CONS, false, "g", [](const DevicePlan &P) { CHECK(!P.general && P.fast_local); });
+        run_case("local 576", loc, B, 3.0, CONS, false, "g", [](const DevicePlan &P) { CHECK(P.general && !P.fast_local); });
+    }
+    {   Sets S; S.uniform(2, 3, 1000); S.add({1000, 1000, 600});      // a ragged set: w = 20 of its long reads, 220 with half of its 400 extra columns
+        // KNOWN DISAGREEMENT (LOG.md, the routing round): the plan takes the wide range from an estimate without the extra columns (120 columns: the 448-column
+        // ring, band half-widths up to 215), the launch's final plan counts them (520 columns: the long-read ring, up to 343).  size_arenas sizes set 2 for the
+        // narrow loop and direction words; on the device its alignments take the wide loop, which in dir_mode 1 writes score records.
+        run_case("ragged set, routed past 40", aff, S, 3.0, CONS, false, "d", [](const DevicePlan &P) {
+            CHECK(!P.general && P.extra[2] == 400 && P.route[2] == 400 && P.weff_hi == 220 && P.ps[2].band_extra == 400 && !P.set_wide[0] && !P.set_wide[1]);
+            CHECK(P.wide_hi == 215 && !P.set_wide[2]); }, {2});
+    }
+    {   Sets S; S.add({3000, 2900}); S.add({3000, 2900, 2950});      // one set, both loops: its longest read takes the wide one, its shortest the narrow one
+        run_case("wide and narrow reads in a set", aff, S, 3.0, CONS, false, "dwg", [](const DevicePlan &P) {
+            CHECK(!P.general && P.max_extra == 0 && P.any_wide_set && P.set_wide[0] && P.set_wide[1] && !P.rounds_possible); });
+    }
+    CHECK(g_routed > 1000);
 }
 
 static void accessor_cases() {
@@ -145,8 +233,9 @@ int main() {
     for (const char *sw : {"ABPOA_HIP_NODIR", "ABPOA_HIP_NOWIDE", "ABPOA_HIP_WIDE_LO", "ABPOA_HIP_DEVICE_GENERAL", "ABPOA_HIP_NOFAST", "ABPOA_HIP_NOXL",
                            "ABPOA_HIP_RING_ROWS", "ABPOA_HIP_DIR_WIDE", "ABPOA_HIP_EXTRA_ROUTE_MIN", "ABPOA_HIP_ARENA_PCT", "ABPOA_HIP_VERBOSE"}) unsetenv(sw);
     plan_cases();
+    routing_cases();
     accessor_cases();
     if (g_fail) { fprintf(stderr, "%d checks failed\n", g_fail); return 1; }
-    printf("device plan ok\n");
+    printf("device plan ok (%d descriptors routed)\n", g_routed);
     return 0;
 }

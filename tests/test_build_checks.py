@@ -61,10 +61,11 @@ def test_assembly_row_loop_kernels_own_its_registers(tmp_path_factory):
 
 
 HOST_RULES = r"""
-// the host mirrors of the kernels' routing rules (engine.h fast_global_job / fast_global_aln, msa_device.h msa_device_set_is_ragged): plain functions, checked on the CPU
+// the pieces of the kernels' routing rules (routing.h) and msa_device.h msa_device_set_is_ragged: plain functions, checked on the CPU
 #include <stdio.h>
 #include <vector>
 #include "engine.h"
+#include "routing.h"
 #include "msa_device.h"
 using namespace abpoa_hip;
 static int fails = 0;
@@ -83,6 +84,19 @@ int main() {
     // ... and which of their alignments: linear gaps below the wide loop's band half-widths only (a ragged set's extra columns count half)
     CHECK(fast_global_aln(LIN, 39, 0) && !fast_global_aln(LIN, 40, 0) && !fast_global_aln(LIN, 20, 40) && fast_global_aln(LIN, 20, 38));
     CHECK(fast_global_aln(AFF, 400, 0) && fast_global_aln(CVX, 40, 512));
+    // half of the extra columns counts as band half-width, rounded down
+    CHECK(route_w(20, 0) == 20 && route_w(20, 1) == 20 && route_w(20, 39) == 39 && route_w(20, 41) == 40 && route_w(0, 401) == 200);
+    // the local row loop: local mode without a band, affine / convex gaps; int16 scores, at most loc_cols columns (575 bases: 576 columns), query codes in LDS
+    CHECK(local_loop_job(AFF, L, -1) && local_loop_job(CVX, L, -1) && !local_loop_job(LIN, L, -1) && !local_loop_job(AFF, L, 10) && !local_loop_job(AFF, G, -1) && !local_loop_job(CVX, X, -1));
+    { LdsPlan P; P.loc_cols = 576; P.q_cap = 576; P.fr_cols = 128;
+      CHECK(local_loop_fits(P, 16, 575) && !local_loop_fits(P, 16, 576) && !local_loop_fits(P, 32, 575) && !local_loop_fits(P, 32, 576) && local_loop_fits(P, 16, 1));
+      CHECK(fast_loop_fits(P, 576) && !fast_loop_fits(P, 577));
+      P.q_cap = 512; CHECK(local_loop_fits(P, 16, 512) && !local_loop_fits(P, 16, 513) && fast_loop_fits(P, 512) && !fast_loop_fits(P, 513));
+      P.loc_cols = 0; P.fr_cols = 0; CHECK(!local_loop_fits(P, 16, 100) && !fast_loop_fits(P, 100)); }
+    // the wide row loop's band half-widths; direction words: mode 1 narrow alignments only, mode 2 all, mode 0 none
+    CHECK(in_wide_range(40, 215, 40) && in_wide_range(40, 215, 215) && !in_wide_range(40, 215, 39) && !in_wide_range(40, 215, 216) && !in_wide_range(1, 0, 0) && !in_wide_range(1, 0, 1));
+    CHECK(wide_range_meets(40, 215, 20, 40) && wide_range_meets(40, 215, 215, 300) && !wide_range_meets(40, 215, 20, 39) && !wide_range_meets(40, 215, 216, 300));
+    CHECK(!dir_for(0, false) && !dir_for(0, true) && dir_for(1, false) && !dir_for(1, true) && dir_for(2, false) && dir_for(2, true));
     // read-sets with ragged read ends: lengths differ by more than an eighth of the longest read, at least 64 bases
     CHECK(!ragged({1000}) && !ragged({1000, 1000, 990}) && !ragged({1000, 875}) && ragged({1000, 874}));
     CHECK(!ragged({300, 236}) && ragged({300, 235}) && ragged({10000, 10000, 8000}) && !ragged({10000, 8750, 9999}));
@@ -93,7 +107,8 @@ int main() {
 
 
 def test_host_routing_rules(tmp_path):
-    """fast_global_job / fast_global_aln (engine.h: shared by dp_common.h takes_fast and the host mirrors in engine.cpp / msa_device.cpp) and
+    """The pieces of routing.h (fast_global_job, fast_global_aln, route_w, local_loop_job, local_loop_fits, fast_loop_fits, the wide range, dir_for: shared by
+    the kernels' takes_* rules, engine.cpp and the device-resident driver's plan) and
     msa_device_set_is_ragged (msa_device.h: which read-sets abpoa_hip_msa_batch runs as a batch of their own) on their truth tables -- host code, no GPU."""
     if not os.path.exists("/opt/rocm/bin/hipcc"):
         pytest.skip("no hipcc")

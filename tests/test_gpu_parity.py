@@ -200,6 +200,28 @@ def test_hip_batch_mixed_widths(engine):
     assert nbatch >= 3
 
 
+def test_fast_loop_and_general_kernel_share_a_launch(engine):
+    """The per-alignment boundary of the flat driver's count of fast alignments (engine.cpp: routing.h for_tail_kernel): linear gaps with e1 = 2, where the
+    narrow row loop takes band half-widths up to 39 and routing.h fast_global_aln sends 40 to the general kernel, both in ONE launch, so 0 < n_fast < n and
+    both kernels are launched.  A launch has one scoring, so the two half-widths come from two reads of seq_lg_gb under one band: the first container (54
+    bases) and the next (50 bases) at -b 39 -f 0.019 give w = 39 + int(1.026) = 40 and 39 + int(0.95) = 39.  Both orders, with and without the trace,
+    each alignment against the oracle."""
+    paths = [p for label, p in CASES if label.startswith("seq_lg_gb/")][:2]
+    cases = []
+    for p in paths:
+        g = dict(H.read_abpg(p))
+        g["wb"] = np.array([39], np.int32); g["wf"] = np.array([0.019], np.float32)
+        cases.append(H.FlatCase(g))
+    ws = [39 + int(np.float32(0.019) * np.float32(c.qlen)) for c in cases]
+    assert ws == [40, 39] and cases[0].sc.gap_mode == 0 and cases[0].sc.gap_ext1 >= 1, ws
+    oracle = [H.run_oracle(c) for c in cases]
+    for order in ([0, 1], [1, 0]):
+        for trace in (True, False):
+            hs = H.run_hip([cases[i] for i in order], want_trace=trace)
+            for i, h in zip(order, hs):
+                H.compare_outs(h, oracle[i], label=f"mixed fast / general launch, order {order} trace={trace} w={ws[i]}")
+
+
 def test_arena_overflow_retry_keeps_traces(engine, monkeypatch):
     """Batches whose arenas are under-sized on purpose (ABPOA_HIP_ARENA_PCT): alignments that overflow are re-run at full width in a second
     pass that re-uses the device arenas; the planes of the alignments that finished in the first pass must still come back intact."""

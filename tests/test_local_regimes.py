@@ -101,7 +101,7 @@ def test_requeried_leaves_the_golden_alone_and_composes_with_rescored():
 def test_every_width_has_the_chunks_body_and_shares_of_the_table(name):
     """rc 0 and 16 bits at every point; the chunk count the oracle's rows have is the table's, and the table's body / NCW / shares follow from that count by
     the selection rules written out again here (dp_local_rows.hip: bodies of 3 / 5 / 9 chunks, NCW = ceil(chunks / 4); rows_local_team: chunks / 4 each, the
-    first chunks % 4 wavefronts one more; rows_local.h takes_local: at most 576 columns)."""
+    first chunks % 4 wavefronts one more; routing.h takes_local: at most 576 columns)."""
     want = sorted({1, 63} | {64 * (n - 1) for n in range(2, 10)} | {64 * n - 1 for n in range(1, 10)} | {15, 16, 47, 48, 576})
     assert sorted(LW.QLENS) == want
     seen = set()

@@ -69,7 +69,7 @@ def plan(golden, bits, wb, noxl=False):
 
 
 def inside(golden, bits, wb, noxl=False):
-    """The alignment takes the wide row loop: wide_on and wide_w_lo <= wb <= wide_w_hi (engine.h takes_wide_band)."""
+    """The alignment takes the wide row loop: wide_on and wide_w_lo <= wb <= wide_w_hi (routing.h takes_wide_band)."""
     on, lo, hi, _ = plan(golden, bits, wb, noxl)
     return on == 1 and lo <= wb <= hi
 
