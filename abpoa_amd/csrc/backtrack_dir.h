@@ -3,6 +3,7 @@
 #include "dir_plane.h"
 #include "rows_fast.h"      // DirFmt, FastFmt
 #include "backtrack.h"      // TailState
+#include "tail_schedule.h"  // spec_start_row
 
 namespace abpoa_hip {
 
@@ -58,17 +59,19 @@ __device__ __forceinline__ bool dir_walk_pair(const DevBatch &b, const AlnDesc &
 //   * The tables are cleared by the working wavefront before its first row, so everything that writes or reads them is ordered behind that by the progress
 //     word (helpers) or by program order (the main walk).
 //   * LDS: the helpers' images, windows and tables lie behind the row loop's score ring; the main walk's region aliases the ring (it walks after the rows).
-//   * Start rows, a function of n_rows alone: 14/16, 11/16 and 6/16 of the graph (late start: 3/4, 1/2, 1/4).  The main walk -- all that is left on the
-//     critical path -- keeps an eighth of the rows, enough for its path to run into the first helper's within that helper's 256 table rows.  A step of a
-//     walk costs about a third of a row of the row loop, and the progress word lags the rows by up to a tile: helper 1 has the time of (n/8 - 64) rows for
-//     3 n/16 rows of walk, helper 2 that of (5 n/16 - 64) rows for 5 n/16, helper 3 all it needs.  A helper that is late only makes the main walk wait
-//     for it as it did before.  Tables (the 256 rows below a start row) and their 16-bit fields are as before: dir_walk_pair bounds cigar indices and columns.
+//   * Start rows, a function of n_rows alone (tail_schedule.h, where the arithmetic is; late start: 3/4, 1/2, 1/4 of the graph).  Each is the LAST row of a
+//     64-row tile: the progress word moves at tile switches only, so such a row is released by the very switch that completes it -- no lag.  Helper 1
+//     starts on the last tile boundary that leaves the main walk 64 rows: the main walk -- all that is left on the critical path -- has 64 .. 127 rows
+//     (it was n/8, 240 - 300 in the late rounds of 1 kb sets) and runs into helper 1's path a few rows into that helper's 256 table rows.  A step of a
+//     walk costs about a third of a row of the row loop; helper r, released at row R_r, has the time of n - 1 - R_r rows: helpers 2 and 3 sit at
+//     geometrically growing distances from the sink (sqrt(D_1 n/3) and n/3 rows) so that each of the three walks fewer than three rows per row of its
+//     time.  A helper that is late only makes the main walk wait for it as it did before.  Measured on 1000 x 50 x 1 kb: 4.58 M ticks per set in the
+//     phase against 6.46 with 14/16, 11/16, 6/16; 15/16, 12/16, 6/16 without tile alignment 5.40; a main walk of 128 .. 191 rows 5.59, of 32 .. 95 rows
+//     5.05 (helper 1 is late).  Tables (the 256 rows below a start row) and their 16-bit fields are as before: dir_walk_pair bounds cigar indices and columns.
+//   * The final pass over the cigar is shared by all four wavefronts (dir_final_pass / helper_final_pass below).
 constexpr int SPEC_PROG_FINAL = 1 << 30, SPEC_PROG_ABANDON = -1;
 constexpr int SPEC_WAIT_POLLS = 1 << 16;      // x two s_sleep 127 (about 16 k cycles): far beyond the longest row loop of an alignment this kernel takes
 __device__ __forceinline__ bool dir_walk_early(const DevBatch &b, const AlnDesc &d) { return b.lds.te_on != 0 && dir_walk_pair(b, d); }
-__device__ __forceinline__ int spec_start_row(const bool early, const int gn, const int r) {
-    return early ? (int)(((long long)gn * (r == 1 ? 14 : (r == 2 ? 11 : 6))) >> 4) : (int)(((long long)gn * (SPEC_WK - r)) / SPEC_WK);
-}
 // byte offsets (from LdsPlan.phase_off) of walk r's region and of the tables, and the region's size
 __device__ __forceinline__ int spec_region(const DevBatch &b, const bool early, const int r, int &bytes, int &pm_off) {
     if (early) { bytes = r == 0 ? b.lds.te_main : b.lds.te_w; pm_off = b.lds.te_main + (SPEC_WK - 1) * b.lds.te_w; return r == 0 ? 0 : b.lds.te_main + (r - 1) * b.lds.te_w; }
@@ -80,6 +83,75 @@ __device__ __forceinline__ int spec_region(const DevBatch &b, const bool early, 
 // reached, exactly as the main wavefront does; the cigar is then a chain -- main, then from the word where main met helper a on, then from where a met b ...
 // spec_ctl: 8 ints per wavefront (ints 0..7: [0] = "tables are clear", set by the main wavefront; helper r: [8r] done, status, words, j, start_i, start_j,
 // steps, met << 16 | index -- -1: walked to the end).  DBR: rows a window holds at most (64 per wavefront when four share the backtrack's LDS).
+// FINAL PASS over the finished cigar, a lane per word: row -> node id, matched bases, reversal (reference abpoa_reverse_cigar, abpoa_align.h:88-96).
+// Word k of the cigar is word k of the main walk while k < c0, then a helper's (a chain of walks: seg_wk / seg_off say whose and from where); words k and
+// n_cigar - 1 - k trade places, so a pair reads and writes only its own two slots of the main walk's words and the pairs can go to any wavefront:
+// wavefront w of nw takes the blocks of 128 pairs w, w + nw, ...  Returns this wavefront's matched bases.
+struct DirSegs { int n_cigar, c[SPEC_WK - 1], wk[SPEC_WK - 1], off[SPEC_WK - 1]; };      // c: words up to the end of segment 0, 1, 2; wk / off: segments 1 .. 3
+__device__ __forceinline__ int dir_final_pass(const DevBatch &b, const AlnDesc &d, const DirSegs &sg, const int w, const int nw) {
+    static_assert(SPEC_WK == 4, "the chain below is written out for four segments");
+    const int lane = threadIdx.x & 63;
+    GLOBAL_AS const uint8_t *row_base = vgpr_ptr(b.row_base + d.row0);
+    GLOBAL_AS const int32_t *row_node_id = vgpr_ptr(b.row_node_id + d.row0);
+    GLOBAL_AS const uint8_t *g_query = vgpr_ptr(b.query + d.query_off);      // (the query straight from HBM: this backtrack needs it nowhere else)
+    GLOBAL_AS uint64_t *cg = vgpr_ptr(b.cigar + d.cigar_off);
+    const int n_cigar = sg.n_cigar;
+    auto fix = [&](uint64_t wv, int &nm) __attribute__((always_inline)) -> uint64_t {
+        const int op = (int)(wv & 0xf);
+        if (op == ABPOA_HIP_CINS) return wv;
+        const int row_ = (int)(wv >> 34);
+        if (op == ABPOA_HIP_CMATCH) { const int q = (int)((wv >> 4) & 0x3fffffffu); nm += (int)row_base[row_] == (int)g_query[q] ? 1 : 0; }
+        return (wv & 0x3ffffffffull) | ((uint64_t)(int64_t)row_node_id[row_] << 34);
+    };
+    int nm = 0;
+    const int half = n_cigar >> 1;
+    const int c0_ = sg.c[0], c1_ = sg.c[1], c2_ = sg.c[2];      // (segments that do not exist are empty)
+    const long long p1_ = (long long)sg.wk[0] * d.cigar_cap + sg.off[0] - c0_, p2_ = (long long)sg.wk[1] * d.cigar_cap + sg.off[1] - c1_,
+            p3_ = (long long)sg.wk[2] * d.cigar_cap + sg.off[2] - c2_;
+    auto rd = [&](int k_) __attribute__((always_inline)) -> uint64_t {      // (a chain of walks: the words of the helpers follow this wavefront's)
+        const long long at_ = k_ < c0_ ? (long long)k_ : (k_ < c1_ ? p1_ + k_ : (k_ < c2_ ? p2_ + k_ : p3_ + k_));
+        return cg[at_];
+    };
+    for (int k = 128 * w + lane; k < half; k += 128 * nw) {      // (two pairs of words per lane and turn: their loads -- the words, then node id and base by row -- overlap)
+        const int k2 = k + 64; const bool v2 = k2 < half;
+        uint64_t wa = rd(k), wc = rd(n_cigar - 1 - k), wa2 = v2 ? rd(k2) : 0, wc2 = v2 ? rd(n_cigar - 1 - k2) : 0;
+        const uint64_t a = fix(wa, nm), c_ = fix(wc, nm);
+        if (b.rev_cigar) { cg[k] = a; cg[n_cigar - 1 - k] = c_; } else { cg[k] = c_; cg[n_cigar - 1 - k] = a; }
+        if (v2) { const uint64_t a2 = fix(wa2, nm), c2 = fix(wc2, nm);
+                  if (b.rev_cigar) { cg[k2] = a2; cg[n_cigar - 1 - k2] = c2; } else { cg[k2] = c2; cg[n_cigar - 1 - k2] = a2; } }
+    }
+    if ((n_cigar & 1) && lane == 0 && w == 0) cg[half] = fix(rd(half), nm);
+    return __builtin_amdgcn_readlane(wave_scan_add_i32(nm), 63);
+}
+// ... on all four wavefronts of a walk (spec_ctl as below, and behind the progress word SPEC_FP_WORDS ints more).  A helper that has published its walk's end --
+// or that there is none -- does not leave: it waits for the main wavefront's word fp[0] = round << 1 | "there is a pass", which the main wavefront writes on
+// EVERY way out of finish_alignment_dir where helpers exist (role 0 and dir_walk_pair):
+//   (1) the walk and the chain of segments ended with status 0: "pass", in front of its own share of the pass, behind the segment table fp[1 .. 10];
+//   (2) anything else -- the row loop's status, a cigar that does not fit, a dead end or NEED_SCORES in the walk, a helper's status taken over in the chain:
+//       "no pass", at the function's one exit (no path of role 0 returns earlier; a job without cigars has no helpers: dir_walk_pair).
+// With "pass" helper r takes the blocks r, r + 4, ..., waits for its stores, leaves its count in fp[10 + r] and then the round in fp[13 + r]; the main wavefront
+// waits for the three (each helper gets here on its own: a wait in a helper is bounded, and none waits for another helper) and adds the counts.
+// Order as in the hand-overs above: one CU, one write-through L1; stores acknowledged (vmcnt(0)) before the word in LDS that tells of them.
+constexpr int SPEC_FP = 8 * SPEC_WK + 1, SPEC_FP_WORDS = 17;
+template <typename T, int GAP>
+__device__ __forceinline__ void helper_final_pass(const DevBatch &b, const AlnDesc &d, const int role, int *spec_ctl, const int gen) {
+    typedef __attribute__((address_space(3))) volatile int lds_vint_t;
+    lds_vint_t *fp = (lds_vint_t *)spec_ctl + SPEC_FP;
+    const int lane = threadIdx.x & 63;
+    int v = fp[0];
+    while ((v >> 1) != gen) { __builtin_amdgcn_s_sleep(4); v = fp[0]; }
+    if (!(v & 1)) return;
+    DirSegs sg;
+    sg.n_cigar = __builtin_amdgcn_readfirstlane(fp[1]);
+#pragma unroll
+    for (int q = 0; q < SPEC_WK - 1; ++q) { sg.c[q] = __builtin_amdgcn_readfirstlane(fp[2 + q]); sg.wk[q] = __builtin_amdgcn_readfirstlane(fp[5 + q]); sg.off[q] = __builtin_amdgcn_readfirstlane(fp[8 + q]); }
+    const int nm = dir_final_pass(b, d, sg, role, SPEC_WK);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) fp[10 + role] = nm;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (lane == 0) fp[13 + role] = gen;
+}
+
 template <typename T, int GAP, int DBR = DBTR>
 __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const AlnDesc &d, AlnOut *out_rec, const TailState &ts, const int role = -1,
                                                      int *spec_ctl = nullptr, const int gen = 0, const int *spec_prog = nullptr) {
@@ -97,7 +169,6 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
     const int lane = threadIdx.x & 63;
     const int gn = d.n_rows, qlen = d.qlen;
     const int o1 = b.o1, o2 = b.o2;
-    GLOBAL_AS const uint8_t *row_base = vgpr_ptr(b.row_base + d.row0);
     GLOBAL_AS const int32_t *row_node_id = vgpr_ptr(b.row_node_id + d.row0);
     GLOBAL_AS const uint32_t *row_pd = vgpr_ptr(b.row_pd + 2 * d.row0);      // (two dwords per row)
     GLOBAL_AS const int32_t *pred_off = vgpr_ptr(b.pred_off + d.poff0), *pred_row = vgpr_ptr(b.pred_row + d.pred0);
@@ -112,7 +183,9 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
     const bool spec_static = role >= 0 && dir_walk_pair(b, d), spec = spec_static && status == 0;
     const bool early = spec_static && dir_walk_early(b, d);      // (the helpers walk under the row loop: header comment)
     // helper r's start row; its table covers the 256 rows below
-    auto start_row = [&](int r_) __attribute__((always_inline)) { return spec_start_row(early, gn, r_); };
+    // (tail_schedule.h; worked out once: the walk asks at every flush of a run)
+    const int sr1 = spec_static ? sgpr(spec_start_row(early, gn, 1)) : 0, sr2 = spec_static ? sgpr(spec_start_row(early, gn, 2)) : 0, sr3 = spec_static ? sgpr(spec_start_row(early, gn, 3)) : 0;
+    auto start_row = [&](int r_) __attribute__((always_inline)) { return r_ == 1 ? sr1 : (r_ == 2 ? sr2 : sr3); };
     const int R_g = spec && role >= 1 ? start_row(role) : 0, R_lo = R_g - SPEC_PM_ROWS + 1;
     int half_lds = b.lds.bt_off + b.lds.bt_bytes_tail, pm_off = 0, reg_off = 0;      // this walk's share of the backtrack region
     if (spec_static) reg_off = spec_region(b, early, role, half_lds, pm_off);
@@ -123,6 +196,7 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
     if (role >= 1) {
         // helper (it has waited for the main wavefront's "tables are clear", which also says the row loop's stores have landed: fast_tail.h): the start cell
         if (!spec) { if (spec_static) helper_out(-1); return; }
+        if (R_g < 1 || R_g > gn - 2) { helper_out(-1); return; }      // (a graph too small for this helper's start row: tail_schedule.h)
         if (early) {      // ... not before the row loop has passed the start row
             bool go = false;
             for (int polls = 0; polls < SPEC_WAIT_POLLS; ++polls) {
@@ -162,8 +236,8 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
             }
         }
     }
-
     int n_cigar = 0, node_s = 0, node_e = 0, query_s = 0, query_e = 0, n_aln = 0, n_match = 0;
+    lds_vint_t *fp = ctl + SPEC_FP; bool fp_told = false;      // the word that sends the helpers into the final pass, or home (helper_final_pass)
     long long win_ticks = 0, walk_ticks = 0; int n_windows = 0, n_general = 0;
     long long dbg_why = 0, dbg_a = 0, dbg_b = 0;      // (dead end of the walk: where and on what, for AlnOut.seg under ABPOA_HIP_DBG bit 8)
     if (spec_static && role == 0 && !early) {      // late start: clear the tables, then let the helpers go (whatever the row loop's status: they wait for this)
@@ -513,40 +587,31 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
         if (status == 0) {
             n_aln = best_j - j;      // (every match and insertion step takes one query base, a deletion none)
             WG_SYNC();
-            // ---- final pass, a lane per word: row -> node id, matched bases, reversal (reference abpoa_reverse_cigar, abpoa_align.h:88-96)
-            GLOBAL_AS const uint8_t *g_query = vgpr_ptr(b.query + d.query_off);
-            auto fix = [&](uint64_t wv, int &nm) __attribute__((always_inline)) -> uint64_t {
-                const int op = (int)(wv & 0xf);
-                if (op == ABPOA_HIP_CINS) return wv;
-                const int row_ = (int)(wv >> 34);
-                // (the query straight from HBM: this backtrack needs it nowhere else)
-                if (op == ABPOA_HIP_CMATCH) { const int q = (int)((wv >> 4) & 0x3fffffffu); nm += (int)row_base[row_] == (int)g_query[q] ? 1 : 0; }
-                return (wv & 0x3ffffffffull) | ((uint64_t)(int64_t)row_node_id[row_] << 34);
-            };
-            int nm = 0;
-            const int half = n_cigar >> 1;
-            static_assert(SPEC_WK == 4, "the chain below is written out for four segments");
-            const int c0_ = seg_len[0], c1_ = c0_ + seg_len[1], c2_ = c1_ + seg_len[2];      // (segments that do not exist are empty)
-            const long long p1_ = (long long)seg_wk[1] * d.cigar_cap + seg_off[1] - c0_, p2_ = (long long)seg_wk[2] * d.cigar_cap + seg_off[2] - c1_,
-                    p3_ = (long long)seg_wk[3] * d.cigar_cap + seg_off[3] - c2_;
-            auto rd = [&](int k_) __attribute__((always_inline)) -> uint64_t {      // (a chain of walks: the words of the helpers follow this wavefront's)
-                const long long at_ = k_ < c0_ ? (long long)k_ : (k_ < c1_ ? p1_ + k_ : (k_ < c2_ ? p2_ + k_ : p3_ + k_));
-                return cg[at_];
-            };
-            for (int k = lane; k < half; k += 128) {      // (two pairs of words per lane and turn: their loads -- the words, then node id and base by row -- overlap)
-                const int k2 = k + 64; const bool v2 = k2 < half;
-                uint64_t wa = rd(k), wc = rd(n_cigar - 1 - k), wa2 = v2 ? rd(k2) : 0, wc2 = v2 ? rd(n_cigar - 1 - k2) : 0;
-                const uint64_t a = fix(wa, nm), c_ = fix(wc, nm);
-                if (b.rev_cigar) { cg[k] = a; cg[n_cigar - 1 - k] = c_; } else { cg[k] = c_; cg[n_cigar - 1 - k] = a; }
-                if (v2) { const uint64_t a2 = fix(wa2, nm), c2 = fix(wc2, nm);
-                          if (b.rev_cigar) { cg[k2] = a2; cg[n_cigar - 1 - k2] = c2; } else { cg[k2] = c2; cg[n_cigar - 1 - k2] = a2; } }
+            // ---- final pass (dir_final_pass above), with the helpers where there are any
+            DirSegs sg; sg.n_cigar = n_cigar;
+            sg.c[0] = seg_len[0]; sg.c[1] = sg.c[0] + seg_len[1]; sg.c[2] = sg.c[1] + seg_len[2];
+#pragma unroll
+            for (int q = 1; q < SPEC_WK; ++q) { sg.wk[q - 1] = seg_wk[q]; sg.off[q - 1] = seg_off[q]; }
+            const bool all_waves = spec_static && role == 0;
+            if (all_waves) {      // (1) of the list at helper_final_pass: the segment table, then the word
+                if (lane == 0) { fp[1] = n_cigar;
+#pragma unroll
+                    for (int q = 0; q < SPEC_WK - 1; ++q) { fp[2 + q] = sg.c[q]; fp[5 + q] = sg.wk[q]; fp[8 + q] = sg.off[q]; } }
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                if (lane == 0) fp[0] = (gen << 1) | 1;
+                fp_told = true;
             }
-            if ((n_cigar & 1) && lane == 0) cg[half] = fix(rd(half), nm);
-            n_match = __builtin_amdgcn_readlane(wave_scan_add_i32(nm), 63);
+            n_match = dir_final_pass(b, d, sg, 0, all_waves ? SPEC_WK : 1);
+            if (all_waves) {
+#pragma unroll
+                for (int r_ = 1; r_ < SPEC_WK; ++r_) { while (fp[13 + r_] != gen) __builtin_amdgcn_s_sleep(1); n_match += fp[10 + r_]; }
+                n_match = __builtin_amdgcn_readfirstlane(n_match);
+            }
             node_e = row_node_id[best_i]; query_e = best_j - 1;
             node_s = row_node_id[start_i]; query_s = start_j - 1;
         }
     }
+    if (spec_static && role == 0 && !fp_told) { if (lane == 0) fp[0] = gen << 1; }      // (2) of the list at helper_final_pass: no pass this round
     if (lane == 0) {
         AlnOut o; for (int i_ = 0; i_ < 6; ++i_) o.seg[i_] = ts.seg[i_];
         o.status = status; o.best_score = best_score; o.best_row = best_i; o.best_col = best_j;

@@ -39,7 +39,10 @@ __device__ __forceinline__ void align_fast_tail(const DevBatch &b, const AlnDesc
     // (DIR: a launch in dir_mode -- its narrow-band alignments left direction words, its wide-band ones score records)
     if constexpr (DIR) {
         if (!takes_dir(b, d)) finish_alignment<T, GAP, FastFmt<T, GAP>::CW>(b, d, out_rec, ts);
-        else if (role >= 0 && dir_walk_pair(b, d)) finish_alignment_dir<T, GAP, 64>(b, d, out_rec, ts, role, spec_ctl, gen, spec_prog);      // (several wavefronts on the walk: windows of 64 rows each)
+        else if (role >= 0 && dir_walk_pair(b, d)) {
+            finish_alignment_dir<T, GAP, 64>(b, d, out_rec, ts, role, spec_ctl, gen, spec_prog);      // (several wavefronts on the walk: windows of 64 rows each)
+            if (role >= 1) helper_final_pass<T, GAP>(b, d, role, spec_ctl, gen);                    // (a helper comes back from its walk, or without one, and shares the final pass)
+        }
         else if (role <= 0) finish_alignment_dir<T, GAP>(b, d, out_rec, ts);
     }
     else finish_alignment<T, GAP, FastFmt<T, GAP>::CW>(b, d, out_rec, ts);

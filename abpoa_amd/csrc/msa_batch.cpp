@@ -44,6 +44,11 @@ void cigar_digest_set(const uint8_t *seq0, int len0, uint64_t value) {      // (
     std::lock_guard<std::mutex> lk(g_dig_mu);
     g_dig[fnv64(seq0, (size_t)len0)] = value;
 }
+namespace { struct LastAln { int32_t v[8]; }; std::unordered_map<uint64_t, LastAln> g_last_aln; }
+void last_aln_set(const uint8_t *seq0, int len0, const int32_t *v8) {
+    std::lock_guard<std::mutex> lk(g_dig_mu);
+    LastAln &r = g_last_aln[fnv64(seq0, (size_t)len0)]; for (int i = 0; i < 8; ++i) r.v[i] = v8[i];
+}
 
 int effective_host_cores() {
     int n = (int)std::thread::hardware_concurrency(); if (n < 1) n = 1;
@@ -315,6 +320,16 @@ unsigned long long abpoa_hip__cigar_digest(const uint8_t *seq0, int len0, int re
     const unsigned long long v = it == g_dig.end() ? 0ull : it->second;
     if (reset) g_dig.clear();
     return v;
+}
+// the last alignment's result record of the read-set whose first read is seq0 (last_aln_set), eight ints; returns 0 when there is none; reset = 1 clears the table afterwards
+int abpoa_hip__last_aln(const uint8_t *seq0, int len0, int *out8, int reset) {
+    using namespace abpoa_hip;
+    std::lock_guard<std::mutex> lk(g_dig_mu);
+    const auto it = seq0 ? g_last_aln.find(fnv64(seq0, (size_t)len0)) : g_last_aln.end();
+    const int found = it == g_last_aln.end() ? 0 : 1;
+    if (found && out8) for (int i = 0; i < 8; ++i) out8[i] = it->second.v[i];
+    if (reset) g_last_aln.clear();
+    return found;
 }
 void abpoa_hip_free_msa_array(abpoa_hip_msa_t *r, int n) { for (int i = 0; r && i < n; ++i) abpoa_hip_free_msa(&r[i]); }
 void abpoa_hip_free_msa(abpoa_hip_msa_t *r) {

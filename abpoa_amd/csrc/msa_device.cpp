@@ -539,6 +539,9 @@ void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::
     const PoaState *hs = (const PoaState *)(hg + L.o_state);
     const int32_t *h_cnode = (const int32_t *)(hg + L.o_cnode), *h_ccov = (const int32_t *)(hg + L.o_ccov); const uint8_t *h_cbase = hg + L.o_cbase;
     need_fb.assign(J.n_sets, 0);
+    std::vector<AlnOut> h_out;      // (tests, with the cigar digests: the result record of every set's last alignment -- msa_batch.h last_aln_set)
+    if (p.dig_on && J.n_sets > 0) { h_out.resize((size_t)J.n_sets);
+            if (hipMemcpy(h_out.data(), p.out, sizeof(AlnOut) * (size_t)J.n_sets, hipMemcpyDeviceToHost) != hipSuccess) h_out.clear(); }
     parallel_ranges(std::min(J.n_threads, 8), J.n_sets, [&](int lo, int hi_) {
         for (int s = lo; s < hi_; ++s) {
             abpoa_hip_msa_t &o_ = out[s];
@@ -551,6 +554,9 @@ void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::
                     hs[s].n_nodes, pl.ps[s].node_cap); continue; }
             o_.n_cells = hs[s].n_cells;
             if (p.dig_on && J.sets[s].n_reads > 0) cigar_digest_set(J.sets[s].seqs[0], J.sets[s].lens[0], hs[s].cigar_dig);
+            if (!h_out.empty() && J.sets[s].n_reads > 1) { const AlnOut &a_ = h_out[(size_t)s];
+                    const int32_t v8[8] = {a_.n_matched_bases, a_.n_aln_bases, a_.node_s, a_.node_e, a_.query_s, a_.query_e, a_.n_cigar, a_.status};
+                    last_aln_set(J.sets[s].seqs[0], J.sets[s].lens[0], v8); }
             if (pl.want_cons && hs[s].n_nodes > 2) {
                 const int len = hs[s].cons_len; const int64_t c0 = pl.ps[s].cons0;
                 o_.cons_len = len;

@@ -53,7 +53,7 @@ __device__ __noinline__ long long rounds_rows(const int slot, const int s_, int 
     return (long long)__builtin_amdgcn_s_memtime();
 }
 // role 0: the wavefront that ran the row loop; role 1: a second wavefront of the workgroup that walks the lower half of the graph at the same time
-// (backtrack_dir.h); ctl: eight ints of static LDS per wavefront, and behind them the row loop's progress word; gen: the round
+// (backtrack_dir.h); ctl: eight ints of static LDS per wavefront, behind them the row loop's progress word and the words of the shared final pass (SPEC_FP); gen: the round
 template <typename T, int GAP, bool DIR>
 __device__ __noinline__ void rounds_tail(const int slot, const int s_, const int role_, int *ctl, const int gen_) {
     const DevBatch &b = g_rounds[UNI(slot)].b; const int s = UNI(s_);
@@ -72,8 +72,8 @@ __global__ void __launch_bounds__(GT, 4) poa_rounds_kernel(const int slot, const
     // Which wavefront runs the one-wave phases.  A workgroup's four wavefronts sit on the four SIMDs of its CU; if it were always wavefront 0, the
     // four workgroups of a CU would run their row loops on the same SIMD while the other three idle.  Each workgroup draws a ticket from a per-CU
     // counter and the wavefront on SIMD (ticket mod 4) does the work.
-    __shared__ int sh_simd[GW], sh_target, sh_walk[8 * SPEC_WK + 1];      // sh_walk: hand-over between the wavefronts of a backtrack; [8 SPEC_WK]: the row loop's progress word
-    if (tid < 8 * SPEC_WK + 1) sh_walk[tid] = 0;
+    __shared__ int sh_simd[GW], sh_target, sh_walk[SPEC_FP + SPEC_FP_WORDS];      // sh_walk: hand-over between the wavefronts of a backtrack; [8 SPEC_WK]: the row loop's progress word; [SPEC_FP ..]: the final pass
+    if (tid < SPEC_FP + SPEC_FP_WORDS) sh_walk[tid] = 0;
     {
         const unsigned hwid = __builtin_amdgcn_s_getreg(63492);      // HW_REG_HW_ID: simd_id [5:4], cu_id [11:8], sh_id [12], se_id [15:13]
         if ((tid & 63) == 0) sh_simd[tid >> 6] = (int)((hwid >> 4) & 3);
