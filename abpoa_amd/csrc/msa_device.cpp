@@ -438,6 +438,7 @@ int queue_job(Job &J, DeviceDebug &dbg) {
         if (p.order_mode) { HIP_OK(launch_poa_order(p, st), ABPOA_HIP_ELAUNCH); if (stage("row order", k)) return ABPOA_HIP_ELAUNCH; dbg.order_check(k); }
         HIP_OK(launch_poa_prepare(p, st), ABPOA_HIP_ELAUNCH);
         if (stage("prepare", k)) return ABPOA_HIP_ELAUNCH;
+        dbg.prepare_check(k);
         HIP_OK(hipEventRecord(e[0], st), ABPOA_HIP_ELAUNCH);
         if (pl.general) { HIP_OK(launch_dp_general(b, st), ABPOA_HIP_ELAUNCH); HIP_OK(hipEventRecord(e[1], st), ABPOA_HIP_ELAUNCH); }
         else HIP_OK(launch_dp_fast(b, st, e[1]), ABPOA_HIP_ELAUNCH);

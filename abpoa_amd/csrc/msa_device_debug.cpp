@@ -81,6 +81,80 @@ void DeviceDebug::order_check(int k) {
     }
 }
 
+// after every prepare: the tables the DP reads -- row_base, row_node_id, row_remain, pred_off, pred_row, row_pd, row_sdist and, for general jobs, out_off /
+// out_row -- against a plain serial recomputation from the device's row order and the host graph that was fed the same cigars (graph_check has compared
+// that graph with the device's, edge lists in order).  The remaining length comes from PoaGraph::topological_sort(true), the reference's reverse walk, and is
+// compared by node: the two layers need not agree on the row order.  A wrong remaining length only moves a band and a wrong row_sdist only changes which rows
+// keep their records; neither has to change a consensus, so nothing else notices them.
+void DeviceDebug::prepare_check(int k) {
+    if (!on_) return;
+    const PoaDev &p = *p_; const std::vector<PoaSet> &ps = *ps_;
+    for (int s = 0; s < (int)graphs_.size(); ++s) {
+        if (k >= sets_[s].n_reads) continue;
+        PoaState hst; (void)hipMemcpy(&hst, (uint8_t *)p.state + sizeof(PoaState) * s, sizeof(hst), hipMemcpyDeviceToHost);
+        if (hst.status != POA_ST_OK) continue;
+        const PoaSet &S = ps[s]; const int n = hst.n_nodes;
+        PoaGraph &G = graphs_[s]; int bad = 0;
+        // (the sort only rebuilds the graph's order and remaining-length tables from its nodes: order_check repeats it without the remaining length before it
+        //  reads the order, graph_check and the consensus / MSA checks read nodes and edges only, add_alignment marks the graph unsorted again)
+        try { G.topological_sort(true); } catch (...) { fprintf(stderr, "[poa-device]   set %d round %d: host sort failed\n", s, k); continue; }
+        if (G.n_nodes() != n) { fprintf(stderr, "[poa-device]   set %d round %d: prepare check FAILED: node count %d vs host %d\n", s, k, n, G.n_nodes()); continue; }
+        std::vector<int32_t> order(n), row(n, -1), rem(n), nid(n), poff(n + 1), ooff; std::vector<uint8_t> base(n), sd(n); std::vector<uint32_t> pd(2 * (size_t)n);
+        bool dl_ok = true;      // (a table that did not arrive is a failed check, not a comparison with whatever the buffer held)
+        auto dl = [&](void *dst, const void *src, size_t bytes) { if (bytes && hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) dl_ok = false; };
+        dl(order.data(), p.row_node[hst.order_buf] + S.node0, 4 * (size_t)n); dl(rem.data(), p.row_remain + S.node0, 4 * (size_t)n);
+        dl(nid.data(), p.row_node_id + S.node0, 4 * (size_t)n); dl(poff.data(), p.pred_off + S.node0, 4 * (size_t)(n + 1));
+        dl(base.data(), p.row_base + S.node0, (size_t)n); dl(sd.data(), p.row_sdist + S.node0, (size_t)n); dl(pd.data(), p.row_pd + 2 * S.node0, 8 * (size_t)n);
+        auto complain = [&](const char *what, int r, long long got, long long want) { if (bad++ < 6) fprintf(stderr,
+                "[poa-device]   set %d round %d: row %d: %s %lld, host %lld\n", s, k, r, what, got, want); };
+        bool usable = true;
+        for (int r = 0; r < n; ++r) { if (order[r] < 0 || order[r] >= n || row[order[r]] >= 0) { complain("row order entry", r, order[r], -1); usable = false; } else row[order[r]] = r; }
+        if (usable) {
+            // the lists as one serial pass writes them: predecessors in in_id order (row 0 has none), successors in out_id order
+            std::vector<int32_t> want_poff(n + 1, 0), want_pred, want_ooff(n + 1, 0), want_out;
+            for (int r = 0; r < n; ++r) {
+                const PoaNode &h = G.node(order[r]);
+                want_poff[r] = (int32_t)want_pred.size(); if (r > 0) for (int t = 0; t < (int)h.in_id.size(); ++t) want_pred.push_back(row[h.in_id[t]]);
+                want_ooff[r] = (int32_t)want_out.size(); for (int t = 0; t < (int)h.out_id.size(); ++t) want_out.push_back(row[h.out_id[t]]);
+            }
+            want_poff[n] = (int32_t)want_pred.size(); want_ooff[n] = (int32_t)want_out.size();
+            std::vector<int32_t> pred(std::max<size_t>(1, want_pred.size())), outr;
+            if ((long long)want_pred.size() <= S.pred_cap) dl(pred.data(), p.pred_row + S.pred0, 4 * want_pred.size());
+            else complain("predecessor entries beyond the set's slots, set still ok:", n, (long long)want_pred.size(), S.pred_cap);
+            if (p.out_off) { ooff.resize(n + 1); dl(ooff.data(), p.out_off + S.node0, 4 * (size_t)(n + 1)); outr.resize(std::max<size_t>(1, want_out.size()));
+                             if ((long long)want_out.size() <= S.pred_cap) dl(outr.data(), p.out_row + S.pred0, 4 * want_out.size()); }
+            for (int r = 0; r < n; ++r) {
+                const int u = order[r]; const PoaNode &h = G.node(u);
+                if (base[r] != h.base) complain("row_base", r, base[r], h.base);
+                if (nid[r] != u) complain("row_node_id", r, nid[r], u);
+                const int want_rem = p.banded ? G.remain()[u] : 0;
+                if (rem[r] != want_rem) complain("remaining length", r, rem[r], want_rem);
+                if (poff[r] != want_poff[r]) complain("pred_off", r, poff[r], want_poff[r]);
+                const int np = want_poff[r + 1] - want_poff[r]; unsigned long long want_pd = ~0ull;
+                for (int t = 0; t < np; ++t) {
+                    const int pr = want_pred[want_poff[r] + t];
+                    if ((long long)want_pred.size() <= S.pred_cap && pred[want_poff[r] + t] != pr) complain("pred_row entry", r, pred[want_poff[r] + t], pr);
+                    if (t < 8 && r - pr <= 254) want_pd = (want_pd & ~(0xffull << (8 * t))) | ((unsigned long long)(r - pr) << (8 * t));
+                }
+                const unsigned long long got_pd = (unsigned long long)pd[2 * (size_t)r] | ((unsigned long long)pd[2 * (size_t)r + 1] << 32);
+                if (got_pd != want_pd) complain("row_pd (low dword shown)", r, (long long)(uint32_t)got_pd, (long long)(uint32_t)want_pd);
+                int far = 0; for (int t = 0; t < (int)h.out_id.size(); ++t) far = std::max(far, row[h.out_id[t]]);
+                const int want_sd = far >= n - 1 ? 255 : std::min(std::max(far - r, 0), 255);      // (the sink is the last row)
+                if (sd[r] != want_sd) complain("row_sdist", r, sd[r], want_sd);
+                if (p.out_off) {
+                    if (ooff[r] != want_ooff[r]) complain("out_off", r, ooff[r], want_ooff[r]);
+                    if ((long long)want_out.size() <= S.pred_cap) for (int t = want_ooff[r]; t < want_ooff[r + 1]; ++t) if (outr[t] != want_out[t]) complain("out_row entry", r, outr[t], want_out[t]);
+                }
+            }
+            if (poff[n] != want_poff[n]) complain("pred_off[n]", n, poff[n], want_poff[n]);
+            if (p.out_off && ooff[n] != want_ooff[n]) complain("out_off[n]", n, ooff[n], want_ooff[n]);
+        }
+        if (!dl_ok) { fprintf(stderr, "[poa-device]   set %d round %d: prepare check FAILED: download failed\n", s, k); continue; }
+        fprintf(stderr, "[poa-device]   set %d round %d: prepare check %s (%d rows, %d differences)%s\n", s, k, bad ? "FAILED" : "ok", n, bad,
+                p.out_off ? " successor rows too" : "");
+    }
+}
+
 // after every fuse: sets 0..3 structurally and against the host graph fed with the same cigars
 void DeviceDebug::graph_check(int k) {
     if (!on_) return;

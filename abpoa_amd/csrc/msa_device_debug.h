@@ -22,6 +22,7 @@ public:
     bool on() const { return on_; }
     int stage(const char *what, int k);                     // synchronise and report; != 0: the stream is in error
     void order_check(int k);                                // row order of round k against the host graph's Kahn walk (order_mode 1)
+    void prepare_check(int k);                              // after the prepare of round k: the DP's row tables against a serial recomputation from the host graph
     void graph_check(int k);                                // after the fuse of round k: device graph against the host graph fed the same cigar
     void balance_report(int k, const DevBatch &b, hipEvent_t rows_begin, hipEvent_t rows_end);      // ABPOA_HIP_IMBAL: slowest / mean alignment of the round, censuses
     void msa_check(const PoaState *hs, const abpoa_hip_msa_t *out);

@@ -121,9 +121,60 @@ __global__ void __launch_bounds__(GT) poa_strand_pick_kernel(const PoaDev p) {
 // score[u] = w* + score[t*] where w* is the largest out-edge weight and t* the target with the best score among the
 // edges of weight w* (ties: the LAST such edge; for the source: best weight, then best score, ties: the FIRST).  The
 // reference fills these in a reverse Kahn walk; they are functions of the successors only, so any reverse topological
-// order gives the same values.  Here: 64-row blocks from the sink upwards, lane = row; inside a block a lane fires as soon
-// as the in-block targets among its heaviest edges are done (their scores travel through LDS), everything above the block
-// is final in HBM.  Then the path is walked from the source, block by block through LDS.
+// order gives the same values.  Here: 64-row blocks from the sink upwards, lane = row, one wavefront per read-set, in three parts.
+//   * LOADS, three blocks deep.  What a row needs before any score -- its node, that node's out-degree with the hot weights and ids (one int4 each), the
+//     rows of the targets of its heaviest edges -- is a chain of three dependent memory round trips that depends on no score.  While block h resolves,
+//     level 3 of block h - 64, level 2 of h - 128 and level 1 of h - 192 are in flight, so a block waits for about one round trip instead of six.  Nothing
+//     in the loop is a __syncthreads(): its vmcnt(0) would wait for those loads; the wavefront orders its LDS traffic with cons_fence().
+//   * RESOLVE.  A row with ONE heaviest edge has score = w* + score[target] and no choice to make: chains of such rows inside the block collapse by pointer
+//     jumping over the lanes (six steps of ds_bpermute; a row that runs into a row WITH a choice stops there, the weights summed so far kept).  Rows with
+//     several heaviest edges fire as soon as the in-block targets among them are done (scores through LDS), by the reference's tie rules.  Scores of the
+//     block above come from LDS; a target further up is final in HBM and is read once the stores are acknowledged (rare: a jump over a whole block).  Rows
+//     with five to eight out-edges have their first cold slots in flight with level 3; rows with more load their lists here, as they always did.
+//   * PATH.  The chain of chosen successors is walked from the source with the block's successor rows in registers (v_readlane, no memory in the walk);
+//     the rows it visits form a lane mask, and the lanes of the mask emit the block's records together: position = length so far + rank in the mask (a
+//     successor's row is always larger).  The next block's rows are requested together with the loads of the records; a path that jumps elsewhere loads again.
+namespace {
+// What the score pass keeps in flight per row (lane = row of a 64-row block), level by level; level k of block h - 64 k is issued while block h resolves.
+struct ConsNode {      // level 2: the row's node, its out-degree (0: no row), the hot weights and ids
+    int u = 1, no = 0;
+    int4 w = make_int4(0, 0, 0, 0), o = make_int4(0, 0, 0, 0);
+};
+struct ConsRow {       // level 3: what the row's turn needs
+    int u = 1, no = 0, wmax = INT_MIN;                       // wmax: the heaviest HOT weight
+    int hw[POA_HOT] = {0, 0, 0, 0};                          // the hot weights
+    int rr[POA_HOT] = {-1, -1, -1, -1};                      // row of the target of hot edge t; -1: no such edge, or (a row without cold slots) not one of the heaviest
+    int cw[POA_HOT] = {0, 0, 0, 0}, co[POA_HOT] = {0, 0, 0, 0};      // a row with POA_HOT + 1 .. mid_max out-edges: weights and ids of its first cold slots
+};
+__device__ __forceinline__ ConsNode cons_level2(const PoaDev &p, const int64_t N0, const int u, const bool valid) {
+    ConsNode a; a.u = u;
+    if (valid) {
+        a.no = (int)p.nd_nout[N0 + u];
+        a.w = *(const int4 *)(p.nd_outw + (N0 + u) * POA_HOT);
+        a.o = *(const int4 *)(p.nd_out + (N0 + u) * POA_HOT);
+    }
+    return a;
+}
+// A row without cold slots: the rows of the targets of its heaviest edges.  A row with five to eight out-edges (one backbone node in ten of a 50-read graph):
+// the rows of ALL its hot targets and its first four cold slots, so that its turn loads nothing unless a cold edge is among the heaviest.
+__device__ __forceinline__ ConsRow cons_level3(const PoaDev &p, const int64_t N0, const ConsNode &a, const bool valid, const int mid_max) {
+    ConsRow b; b.u = a.u; b.no = valid ? a.no : 0;
+    const int w[POA_HOT] = {a.w.x, a.w.y, a.w.z, a.w.w}, o[POA_HOT] = {a.o.x, a.o.y, a.o.z, a.o.w};
+#pragma unroll
+    for (int t = 0; t < POA_HOT; ++t) { b.hw[t] = w[t]; if (t < a.no) b.wmax = imax_(b.wmax, w[t]); }
+    const bool hot = valid && a.no <= POA_HOT, mid = valid && a.no > POA_HOT && a.no <= mid_max;
+#pragma unroll
+    for (int t = 0; t < POA_HOT; ++t) if ((hot && t < a.no && w[t] == b.wmax) || mid) b.rr[t] = p.nd_row[N0 + o[t]];
+    if (mid) {
+        const int64_t Xc = (N0 + a.u) * (p.out_cap - POA_HOT);
+#pragma unroll
+        for (int t = 0; t < POA_HOT; ++t) if (POA_HOT + t < a.no) { b.cw[t] = p.nd_outwx[Xc + t]; b.co[t] = p.nd_outx[Xc + t]; }
+    }
+    return b;
+}
+// orders this wavefront's LDS traffic and nothing else (one wavefront per read-set: no s_barrier needed)
+__device__ __forceinline__ void cons_fence() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); }
+}  // namespace
 __global__ void __launch_bounds__(64) poa_consensus_kernel(const PoaDev p) {
     const int s = blockIdx.x, lane = threadIdx.x;
     if (s >= p.n_sets) return;
@@ -136,35 +187,99 @@ __global__ void __launch_bounds__(64) poa_consensus_kernel(const PoaDev p) {
     const int32_t *order = p.row_node[st->order_buf] + N0;
     int32_t *score = p.row_remain + N0;          // per ROW (pools of the DP inputs, free after the last round)
     int32_t *nextrow = p.row_node_id + N0;       // per row: row of the chosen successor (-1: none)
-    __shared__ int sh_score[64], sh_next[64], sh_node[64];
-    for (int t0 = ((n - 1) >> 6) << 6; t0 >= 0; t0 -= 64) {
-        const int r = t0 + lane; const bool valid = r < n;
-        const int u = valid ? order[r] : 1;
-        const int no = valid ? (int)p.nd_nout[N0 + u] : 0;
-        // heaviest weight and the rows of the candidate targets (edges with that weight), as a dependency mask inside the block
-        int wmax = INT_MIN;
-        for (int t = 0; t < no; ++t) wmax = imax_(wmax, outw_slot(p, S, N0 + u, t));
+    __shared__ int sh_score[64], sh_above[64];       // scores of the block being resolved / of the block above it (lane = row - block start)
+    constexpr int NCAND = 4;
+    static_assert(POA_HOT == 4 && NCAND == POA_HOT, "the hot slots are read as one int4 and are the candidates of a row without cold slots");
+    const int top = ((n - 1) >> 6) << 6;
+    // the loads in flight (see above): level 1 of block h - 192, level 2 of h - 128, level 3 of h - 64; a lane beyond the graph (before row 0 too) has no edges
+    const int mid_max = imin_(2 * POA_HOT, p.out_cap);
+    auto in_graph = [&](int r_) { return r_ >= 0 && r_ < n; };
+    int u1 = 1; ConsNode node2; ConsRow row3;
+    sh_above[lane] = 0;
+    for (int h = top + 192; h >= 0; h -= 64) {
+        const ConsRow cur = row3;                                               // block h: everything arrived
+        row3 = cons_level3(p, N0, node2, in_graph(h - 64 + lane), mid_max);
+        node2 = cons_level2(p, N0, u1, in_graph(h - 128 + lane));
+        u1 = in_graph(h - 192 + lane) ? order[h - 192 + lane] : 1;              // level 1: the row's node
+        if (h > top) continue;                                                  // (the first three turns only fill the pipeline)
+        const int u = cur.u, no = cur.no; int wmax = cur.wmax;
+        const int t0 = h, r = t0 + lane; const bool valid = r < n;
+        const bool mid = no > POA_HOT && no <= mid_max;
+        const bool slow = no > POA_HOT && !mid;                                 // more cold slots than travel with the row (the source of a ragged set: up to POA_TERM_MAX edges)
         // candidates = targets of the heaviest edges, in edge order: their rows (and, for targets in later blocks, their final scores)
-        // are fetched once, so that a row's turn in the loop below costs LDS reads only; a row with more than NCAND candidates re-reads
-        constexpr int NCAND = 4;
-        unsigned long long dep = 0; int ctr[NCAND], csc[NCAND], ncand = 0;
+        // are at hand before the row's turn, which then costs LDS reads only; a row with more than NCAND candidates re-reads
+        unsigned long long dep = 0; int ctr[NCAND], csc[NCAND], ncand = 0; bool far = false;
 #pragma unroll
         for (int c_ = 0; c_ < NCAND; ++c_) { ctr[c_] = -1; csc[c_] = 0; }
-        for (int t = 0; t < no; ++t) if (outw_slot(p, S, N0 + u, t) == wmax) {
-            const int tr = p.nd_row[N0 + out_slot(p, S, N0 + u, t)];
-            if (tr < t0 + 64) dep |= 1ull << (tr - t0);
+        if (mid) {      // the heaviest weight over hot and cold slots; a hot edge that has it is a candidate; the row of a cold one is loaded now
 #pragma unroll
-            for (int c_ = 0; c_ < NCAND; ++c_) if (c_ == ncand) { ctr[c_] = tr; csc[c_] = tr >= t0 + 64 ? ld_fresh(score + tr) : 0; }
-            ++ncand;
+            for (int t = 0; t < POA_HOT; ++t) if (POA_HOT + t < no) wmax = imax_(wmax, cur.cw[t]);
         }
-        bool done = !valid; int my_score = 0, my_next = -1;
-        if (valid && no == 0) { done = true; }                                  // the sink: score 0, no successor
+        if (!slow) {
+#pragma unroll
+            for (int t = 0; t < POA_HOT; ++t) if (cur.rr[t] >= 0 && (!mid || cur.hw[t] == wmax)) {
+#pragma unroll
+                for (int c_ = 0; c_ < NCAND; ++c_) if (c_ == ncand) ctr[c_] = cur.rr[t];
+                ++ncand;
+            }
+            if (mid) {
+#pragma unroll
+                for (int t = 0; t < POA_HOT; ++t) if (POA_HOT + t < no && cur.cw[t] == wmax) {
+                    const int tr = p.nd_row[N0 + cur.co[t]];
+                    if (tr < t0 + 64) dep |= 1ull << (tr - t0);      // (also for a candidate beyond the NCAND that are kept)
+#pragma unroll
+                    for (int c_ = 0; c_ < NCAND; ++c_) if (c_ == ncand) ctr[c_] = tr;
+                    ++ncand;
+                }
+                if (ncand > NCAND) far = true;      // (its turn re-reads every candidate's score from memory: behind the wait below, like every such read)
+            }
+#pragma unroll
+            for (int c_ = 0; c_ < NCAND; ++c_) if (c_ < ncand) {
+                if (ctr[c_] < t0 + 64) dep |= 1ull << (ctr[c_] - t0);
+                else if (ctr[c_] < t0 + 128) csc[c_] = sh_above[ctr[c_] - t0 - 64];
+                else far = true;
+            }
+        }
+        if (__any(slow || far)) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // stores are write-through: once acknowledged, the scores of the blocks above are read from L2 (ld_fresh)
+            if (slow) {
+                wmax = INT_MIN;
+                for (int t = 0; t < no; ++t) wmax = imax_(wmax, outw_slot(p, S, N0 + u, t));
+                for (int t = 0; t < no; ++t) if (outw_slot(p, S, N0 + u, t) == wmax) {
+                    const int tr = p.nd_row[N0 + out_slot(p, S, N0 + u, t)];
+                    if (tr < t0 + 64) dep |= 1ull << (tr - t0);
+#pragma unroll
+                    for (int c_ = 0; c_ < NCAND; ++c_) if (c_ == ncand) { ctr[c_] = tr; csc[c_] = tr >= t0 + 64 ? ld_fresh(score + tr) : 0; }
+                    ++ncand;
+                }
+            } else if (far) {
+#pragma unroll
+                for (int c_ = 0; c_ < NCAND; ++c_) if (c_ < ncand && ctr[c_] >= t0 + 128) csc[c_] = ld_fresh(score + ctr[c_]);
+            }
+        }
+        bool done = !valid || no == 0; int val = 0, my_next = -1;               // (the sink: score 0, no successor)
+        // rows with one heaviest edge: score = acc + score[tgt], tgt moving down the chain until it is a finished row or a row with a choice
+        const bool simple = valid && !slow && ncand == 1;
+        int acc = wmax, tgt = simple ? ctr[0] : r;
+        if (simple) { my_next = ctr[0]; if (ctr[0] >= t0 + 64) { val = wmax + csc[0]; done = true; } }
+        if (__any(simple && !done)) {
+#pragma unroll
+            for (int it = 0; it < 6; ++it) {
+                const bool jump = simple && !done;
+                const int src = jump ? tgt - t0 : lane;
+                const int t_tgt = shfl(tgt, src), t_acc = shfl(acc, src), t_val = shfl(val, src), t_st = shfl((int)done | ((int)jump << 1), src);
+                if (jump) { if (t_st & 1) { val = acc + t_val; done = true; } else if (t_st & 2) { acc += t_acc; tgt = t_tgt; } }
+            }
+        }
+        if (simple && !done) dep = 1ull << (tgt - t0);                          // (stopped at a row with a choice: fires behind it)
+        int my_score = val;
         unsigned long long done_mask = __ballot(done);
-        sh_score[lane] = 0; sh_next[lane] = -1;
-        __syncthreads();
+        sh_score[lane] = val;
+        cons_fence();
         for (int it = 0; it < 64 && done_mask != ~0ull; ++it) {
             const bool fire = !done && (dep & ~done_mask) == 0;
-            if (fire) {
+            if (fire && simple) { my_score = acc + sh_score[tgt - t0]; done = true; sh_score[lane] = my_score; }
+            else if (fire) {
                 int best_sc = INT_MIN, best_row = -1; const bool is_src = u == 0;
                 if (ncand <= NCAND) {
 #pragma unroll
@@ -175,35 +290,45 @@ __global__ void __launch_bounds__(64) poa_consensus_kernel(const PoaDev p) {
                     }
                 } else for (int t = 0; t < no; ++t) if (outw_slot(p, S, N0 + u, t) == wmax) {
                     const int tr = p.nd_row[N0 + out_slot(p, S, N0 + u, t)];
+                    // INVARIANT: every ld_fresh(score + ...) of this loop body sits behind the block's vmcnt(0) above.  A row gets here with more than NCAND
+                    // candidates only: a slow row (the wait is taken for any slow row) or a mid row, which set `far` for exactly this read.  Keep both.
                     const int sc_ = tr < t0 + 64 ? sh_score[tr - t0] : ld_fresh(score + tr);
                     if (best_row < 0 || (is_src ? sc_ > best_sc : sc_ >= best_sc)) { best_sc = sc_; best_row = tr; }
                 }
                 my_score = wmax + best_sc; my_next = best_row; done = true;
                 sh_score[lane] = my_score;
             }
-            __syncthreads();
+            cons_fence();
             done_mask |= __ballot(fire);
         }
         if (valid) { score[r] = my_score; nextrow[r] = my_next; }
-        __syncthreads();
+        sh_above[lane] = my_score;
+        cons_fence();
     }
     // ---- path: rows from the source's choice to the sink
-    int cur = ld_fresh(nextrow + 0), len = 0; bool overflow = false;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // (the successor rows are read back from L2)
+    int cur = uni(ld_fresh(nextrow + 0)), len = 0; bool overflow = false;
     const int sink_row = n - 1;                   // the sink is always the last row
+    int pf_t0 = -1, pf_next = -1, pf_node = 0;    // the block behind the one being walked, requested ahead
     while (cur >= 0 && cur < sink_row) {
         const int t0 = cur & ~63;
         const int r = t0 + lane;
-        sh_next[lane] = r < n ? ld_fresh(nextrow + r) : -1;
-        sh_node[lane] = r < n ? order[r] : 0;
-        __syncthreads();
+        int nx, nd;
+        if (t0 == pf_t0) { nx = pf_next; nd = pf_node; }
+        else { nx = r < n ? ld_fresh(nextrow + r) : -1; nd = r < n ? order[r] : 0; }
+        unsigned long long on_path = 0;
         while (cur >= t0 && cur < t0 + 64 && cur < sink_row) {
-            const int u = sh_node[cur - t0];
-            if (len < S.cons_cap) { if (lane == 0) { p.cons_node[S.cons0 + len] = u; p.cons_base[S.cons0 + len] = p.nd_base[N0 + u]; p.cons_cov[S.cons0 + len] = p.nd_nread[N0 + u]; } }
-            else overflow = true;
-            ++len;
-            cur = sh_next[cur - t0];
+            on_path |= 1ull << (cur - t0);
+            const int to = __builtin_amdgcn_readlane(nx, cur - t0);
+            cur = to > cur ? to : -1;             // (a successor's row is larger: anything else ends the path instead of walking in circles)
         }
-        __syncthreads();
+        // (requested behind the walk, next to the loads of the records: one wait for both, and the next turn finds its block arrived)
+        pf_t0 = t0 + 64;
+        pf_next = r + 64 < n ? ld_fresh(nextrow + r + 64) : -1; pf_node = r + 64 < n ? order[r + 64] : 0;
+        const int at = len + __popcll(on_path & ((1ull << lane) - 1ull));
+        if ((on_path >> lane & 1ull) && at < S.cons_cap) { p.cons_node[S.cons0 + at] = nd; p.cons_base[S.cons0 + at] = p.nd_base[N0 + nd]; p.cons_cov[S.cons0 + at] = p.nd_nread[N0 + nd]; }
+        len += __popcll(on_path);
+        if (len > S.cons_cap) overflow = true;
     }
     if (lane == 0) { st->cons_len = len; if (overflow) { st->status = POA_ST_FALLBACK; st->reason = POA_WHY_EDGE_SLOTS; } }      // (a full consensus pool has always reported this code)
 }
