@@ -419,6 +419,12 @@ void abpoa_hip__wide_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max_b
     out[0] = L.wide_on; out[1] = L.wfr_rows; out[2] = L.total_wide; out[3] = L.total_wide > 0 ? abpoa_hip::wide_workgroups_per_cu(L.total_wide) : 0;
     out[4] = L.w_phase_off; out[5] = L.wide_w_lo; out[6] = L.wide_w_hi;
 }
+// (test hook, host only: the same plan's narrow row loop -- out: score-ring rows, score-ring columns (0: no fast loop), arena window of the tail kernel in bytes)
+void abpoa_hip__narrow_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max_bits, int n_aln, int *out) {
+    abpoa_hip::LdsPlan L; const int pn = max_bits == 16 ? 16 : 8; const int w = sc->wb + (int)(sc->wf * (float)max_qlen);
+    abpoa_hip::make_lds_plan(sc, max_qlen, max_bits, abpoa_hip::band_cols(abpoa_hip::padded_width(max_qlen, pn), w, pn, true), n_aln, &L);
+    out[0] = L.fr_rows; out[1] = L.fr_cols; out[2] = L.bt_bytes_tail;
+}
 void abpoa_hip__debug_clocks(long long *out) { for (int i = 0; i < 10; ++i) { out[i] = g_dbg[i]; g_dbg[i] = 0; } }
 void abpoa_hip_reset_stats(void) { std::lock_guard<std::mutex> lk(g.stats_mu); memset(&g.stats, 0, sizeof(g.stats)); }
 

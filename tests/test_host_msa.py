@@ -194,6 +194,25 @@ def test_seeded_sweep_of_the_oracle_backed_host_layer_against_the_reference_cli(
 
 
 @pytest.mark.skipif(not H.have_ref(), reason="reference build not available")
+@pytest.mark.parametrize("kind", ["err30", "ins16", "first_pass"])
+def test_divergent_read_sets_against_the_reference_cli(tmp_path, kind):
+    """The read-set shapes of tests/test_gpu_narrow_bodies.py (50 x 300 at 30 % error, 50 x 300 at 4 / 4 / 16 % substitutions / deletions / insertions, 20 x 300
+    at 30 %; affine 4,0 / 2), whose graphs hold 100 and more nodes of 5-8 predecessors: the oracle-backed host layer, which that file compares the device
+    with, against the compiled reference binary, output text byte for byte (`-r 2`: MSA rows and consensus)."""
+    import narrow_preds as T
+    sets = T.read_sets(kind)
+    assert len(sets) == T.N_SETS[kind]
+    for i, reads in enumerate(sets):
+        reads = list(reads)
+        fa = str(tmp_path / f"{kind}{i}.fa")
+        synth.write_fasta(fa, reads)
+        ref = subprocess.run([os.path.join(H.REF_DIR, "abpoa_ref"), "-O", "4,0", "-E", "2", "-r", "2", fa], capture_output=True, text=True, check=True, timeout=300)
+        r = api.msa_batch([reads], api.Params(**T.AFFINE), out_cons=True, out_msa=True, lib=H.cpu_shim_lib(), n_threads=2)[0]
+        assert r.status == 0
+        assert api.format_output(r, [f"r{j}" for j in range(len(reads))], True, True) == ref.stdout, (kind, i)
+
+
+@pytest.mark.skipif(not H.have_ref(), reason="reference build not available")
 def test_scoring_points_sweep_of_the_oracle_backed_host_layer_against_the_reference_cli(tmp_path):
     """Every point of tests/scoring_points.py (asymmetric matrices, guard pairs, direction-plane caps) x {adaptive band, -b 3 -f 0, -b -1, local, extension,
     extension with -z 40} x {8 x 120 uncut, 7 x 310 with ragged ends}: the oracle-backed host layer -- what tests/test_gpu_scoring.py compares the
