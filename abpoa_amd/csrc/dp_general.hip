@@ -34,8 +34,11 @@ hipError_t launch_dp_general(const DevBatch &b, hipStream_t stream) { return b.n
 hipError_t launch_dp_fast(const DevBatch &b, hipStream_t stream, hipEvent_t after_rows) {
     if (b.n <= 0) return hipSuccess;
     hipError_t e = hipSuccess;
-    if (b.align_mode != ABPOA_HIP_LOCAL_MODE && !b.lds.narrow_off) e = launch_fast_rows(b, stream);
-    if (e == hipSuccess && b.lds.wide_on >= 1 && b.gap_mode != ABPOA_HIP_LINEAR_GAP) e = launch_wide_rows(b, stream);
+    if (b.align_mode != ABPOA_HIP_LOCAL_MODE && !b.lds.narrow_off) { e = launch_fast_rows(b, stream); __atomic_fetch_add(&g_row_launches[0], 1, __ATOMIC_RELAXED); }
+    if (e == hipSuccess && b.lds.wide_on >= 1 && b.gap_mode != ABPOA_HIP_LINEAR_GAP) {
+        e = launch_wide_rows(b, stream);
+        __atomic_fetch_add(&g_row_launches[b.lds.wfr_cols == WIDE_RING_COLS_XL ? 2 : 1], 1, __ATOMIC_RELAXED);
+    }
     if (e == hipSuccess && b.lds.loc_cols > 0 && b.align_mode == ABPOA_HIP_LOCAL_MODE) e = launch_local_rows(b, stream);
     if (e == hipSuccess) e = hipEventRecord(after_rows, stream);
     if (e == hipSuccess) e = launch_fast_tail(b, stream);

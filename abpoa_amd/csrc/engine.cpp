@@ -58,6 +58,7 @@ struct Engine {
 static Engine g;
 long long g_dbg[10] = {0};
 long long g_dir_counts[2] = {0, 0};      // alignments whose backtrack walked a direction plane; alignments redone with score records (NEED_SCORES)
+long long g_row_launches[3] = {0, 0, 0}; // launches of the narrow row kernel, of dp_wide_kernel, of dp_xl_kernel (launch_dp_fast counts, abpoa_hip__row_launches reads)
 
 int engine_device() { return g.ready ? g.device : -1; }
 int device_cu_count(int device) {
@@ -425,6 +426,8 @@ void abpoa_hip__narrow_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max
     abpoa_hip::make_lds_plan(sc, max_qlen, max_bits, abpoa_hip::band_cols(abpoa_hip::padded_width(max_qlen, pn), w, pn, true), n_aln, &L);
     out[0] = L.fr_rows; out[1] = L.fr_cols; out[2] = L.bt_bytes_tail;
 }
+// (test hook, host only, read-only for the engine: row-kernel launches since the last call -- narrow loop, 448-column wide loop, 704-column wide loop)
+void abpoa_hip__row_launches(long long *out) { for (int i = 0; i < 3; ++i) out[i] = __atomic_exchange_n(&abpoa_hip::g_row_launches[i], 0, __ATOMIC_RELAXED); }
 void abpoa_hip__debug_clocks(long long *out) { for (int i = 0; i < 10; ++i) { out[i] = g_dbg[i]; g_dbg[i] = 0; } }
 void abpoa_hip_reset_stats(void) { std::lock_guard<std::mutex> lk(g.stats_mu); memset(&g.stats, 0, sizeof(g.stats)); }
 

@@ -145,6 +145,7 @@ int lds_fixed_bytes_bt();
 void make_lds_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max_bits, int64_t est_cols, int n_aln, LdsPlan *L);
 int wide_workgroups_per_cu(int total_wide);
 
+extern long long g_row_launches[3];      // (engine.cpp; diagnostic)
 // Launches the DP kernel for the whole batch on `stream`.
 hipError_t launch_dp(const DevBatch &b, int n_fast, hipStream_t stream, hipEvent_t after_rows);
 hipError_t launch_dp_fast(const DevBatch &b, hipStream_t stream, hipEvent_t after_rows);

@@ -365,7 +365,9 @@ def test_long_read_rows_take_the_all_chunk_bodies(tmp_path):
     into the key's value bits and declined nearly every row.)  Then, with the same library through the flat API, the re-banded 1 kb goldens of
     tests/test_gpu_wide_bodies.py at 6, 7, 8-9 and 11 chunks and at the last band of the 448-column kernel: rows declined as "wider than the body" = the
     oracle's count of such rows, 9-11-chunk rows in the run's own width only, at most 10 % of the rows declined for any other reason (measured: 1.3 % at most,
-    LOG.md round 12 -- a condition on the inputs: move a band that fails it, do not raise the cap)."""
+    LOG.md round 12 -- a condition on the inputs: move a band that fails it, do not raise the cap).  The same on the skip-edge families `far`, `many` and
+    `in_ring` of tests/wide_preds.py at wb = 130 and 250: the rows declined as "not eligible" (slot 1) == the rows with more than 8 predecessors or a predecessor
+    64 and more rows back, counted on the inputs -- so tile bit 19 is false on exactly those rows and the eligible ones reached the bodies."""
     import re
     import subprocess
     import sys
@@ -397,14 +399,18 @@ def test_long_read_rows_take_the_all_chunk_bodies(tmp_path):
     # (a row of 9-11 chunks also in bits 32-47 / 48-62 for int32 / int16), 1 not eligible, 2 ring / geometry, 3 wider than the body's chunks, 4 vectors beyond
     # every predecessor's band outside the last chunk, 5 the body declined (arg-max key window, wrap guard).
     import json
-    r = subprocess.run([sys.executable, "-c", _WIDE_BODY_COUNTERS % dict(root=ROOT, points=WIDE_BODY_POINTS)], capture_output=True, text=True,
+    points = WIDE_BODY_POINTS + WIDE_PRED_POINTS
+    r = subprocess.run([sys.executable, "-c", _WIDE_BODY_COUNTERS % dict(root=ROOT, points=points)], capture_output=True, text=True,
                        env=dict(os.environ, ABPOA_HIP_LIB=lib, ABPOA_HIP_DBG="128"), timeout=600)
     assert r.returncode == 0 and "DONE" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
     recs = [json.loads(ln[4:]) for ln in r.stdout.splitlines() if ln.startswith("ROW ")]
-    assert len(recs) == len(WIDE_BODY_POINTS)
+    assert len(recs) == len(points)
+    import wide_preds as WP
     for rec in recs:
         print("wide-body counters", json.dumps(rec))
-        golden, bits, wb, noxl = rec["point"]
+        golden, bits, wb, noxl, family = rec["point"]
+        # slot 1 ("not eligible": more than 8 predecessors, or one 64 and more rows back) == the count tests/test_wide_pred_regimes.py takes from the inputs
+        assert rec["seg"][1] == rec["not_eligible"] == (WP.NOT_ELIGIBLE[family][("s1k_ag_gb", "s1k_cg_gb").index(golden)] if family else 0), rec
         seg, chunks = rec["seg"], {int(k): v for k, v in rec["chunks"].items()}      # chunks: per count, the oracle's rows 1 .. n - 2 (the rows a body may take)
         widest = 7 if rec["ring_cols"] == 448 else 11
         body, long32, long16 = seg[0] & 0xffffffff, (seg[0] >> 32) & 0xffff, seg[0] >> 48
@@ -417,23 +423,27 @@ def test_long_read_rows_take_the_all_chunk_bodies(tmp_path):
 
 
 # both goldens x both widths at 6, 7, 8-9 and 11 chunks, and the last band of the 448-column kernel (ABPOA_HIP_NOXL=1), whose 8-chunk rows it declines
-WIDE_BODY_POINTS = [(g, b, wb, 0) for g in ("s1k_ag_gb", "s1k_cg_gb") for b in (16, 32) for wb in (165, 196, 250, 324)] + \
-                   [(g, b, 215, 1) for g in ("s1k_ag_gb", "s1k_cg_gb") for b in (16, 32)]
+WIDE_BODY_POINTS = [(g, b, wb, 0, None) for g in ("s1k_ag_gb", "s1k_cg_gb") for b in (16, 32) for wb in (165, 196, 250, 324)] + \
+                   [(g, b, 215, 1, None) for g in ("s1k_ag_gb", "s1k_cg_gb") for b in (16, 32)]
+# ... and the skip-edge families of tests/wide_preds.py whose rows the wide kernels must decline as "not eligible" (`many` and `in_ring`: 9-11 predecessors;
+# `far`: a predecessor 64 and more rows back), at two bands per width
+WIDE_PRED_POINTS = [(g, b, wb, 0, f) for g in ("s1k_ag_gb", "s1k_cg_gb") for b in (16, 32) for wb in (130, 250) for f in ("far", "many", "in_ring")]
 _WIDE_BODY_COUNTERS = r"""
 import ctypes, json, os, sys
 sys.path.insert(0, %(root)r); sys.path.insert(0, %(root)r + '/tests')
-import helpers as H, wide_bands as WB
+import helpers as H, wide_bands as WB, wide_preds as WP
 from abpoa_amd import ffi
 lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0))
 clk = (ctypes.c_longlong * 10)()
-for golden, bits, wb, noxl in %(points)r:
+for golden, bits, wb, noxl, family in %(points)r:
     g = H.first_golden(golden)
-    c = H.FlatCase(H.rescored(g, WB.point(golden, bits, int(g['qlen'][0])), wb, 0.0))
+    c = H.FlatCase(WP.case_dict(golden, family, bits, wb) if family else H.rescored(g, WB.point(golden, bits, int(g['qlen'][0])), wb, 0.0))
     o = H.run_oracle(c)
     pn = 16 if o.bits == 16 else 8
+    rows = WP.wide_rows(c, o)
     chunks = {}
     for r in range(1, c.n_rows - 1):
-        if o.dp_beg_sn[r] >= 0:
+        if o.dp_beg_sn[r] >= 0 and rows[r].eligible:      # (a row that is not eligible never reaches the body's width test)
             n = ((int(o.dp_end_sn[r]) - int(o.dp_beg_sn[r]) + 1) * pn + 63) // 64
             chunks[n] = chunks.get(n, 0) + 1
     if noxl: os.environ['ABPOA_HIP_NOXL'] = '1'
@@ -442,8 +452,8 @@ for golden, bits, wb, noxl in %(points)r:
     h = H.run_hip([c], want_trace=False)[0]
     lib.abpoa_hip__debug_clocks(clk)
     assert h.status == 0 and o.bits == bits and WB.inside(golden, bits, wb, bool(noxl))
-    H.compare_outs(h, o, label='counters build %%s int%%d wb=%%d' %% (golden, bits, wb))
-    print('ROW ' + json.dumps(dict(point=[golden, bits, wb, noxl], ring_cols=WB.RING_COLS[WB.plan(golden, bits, wb, bool(noxl))[2]], rows=sum(chunks.values()),
-                                   chunks=chunks, seg=[int(clk[4 + i]) for i in range(6)])))
+    H.compare_outs(h, o, label='counters build %%s %%s int%%d wb=%%d' %% (golden, family, bits, wb))
+    print('ROW ' + json.dumps(dict(point=[golden, bits, wb, noxl, family], ring_cols=WB.RING_COLS[WB.plan(golden, bits, wb, bool(noxl))[2]], rows=len(rows),
+                                   not_eligible=WP.not_eligible(rows), chunks=chunks, seg=[int(clk[4 + i]) for i in range(6)])))
 print('DONE')
 """

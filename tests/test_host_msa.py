@@ -198,18 +198,22 @@ def test_seeded_sweep_of_the_oracle_backed_host_layer_against_the_reference_cli(
 def test_divergent_read_sets_against_the_reference_cli(tmp_path, kind):
     """The read-set shapes of tests/test_gpu_narrow_bodies.py (50 x 300 at 30 % error, 50 x 300 at 4 / 4 / 16 % substitutions / deletions / insertions, 20 x 300
     at 30 %; affine 4,0 / 2), whose graphs hold 100 and more nodes of 5-8 predecessors: the oracle-backed host layer, which that file compares the device
-    with, against the compiled reference binary, output text byte for byte (`-r 2`: MSA rows and consensus)."""
+    with, against the compiled reference binary, output text byte for byte (`-r 2`: MSA rows and consensus).  Then the same sets at the band of
+    tests/test_gpu_wide_pred_bodies.py (`-b 60 -f 0`: every alignment takes the wide row loop on the device), with affine and with the default convex gaps."""
     import narrow_preds as T
+    import wide_preds as WP
     sets = T.read_sets(kind)
     assert len(sets) == T.N_SETS[kind]
-    for i, reads in enumerate(sets):
-        reads = list(reads)
-        fa = str(tmp_path / f"{kind}{i}.fa")
-        synth.write_fasta(fa, reads)
-        ref = subprocess.run([os.path.join(H.REF_DIR, "abpoa_ref"), "-O", "4,0", "-E", "2", "-r", "2", fa], capture_output=True, text=True, check=True, timeout=300)
-        r = api.msa_batch([reads], api.Params(**T.AFFINE), out_cons=True, out_msa=True, lib=H.cpu_shim_lib(), n_threads=2)[0]
-        assert r.status == 0
-        assert api.format_output(r, [f"r{j}" for j in range(len(reads))], True, True) == ref.stdout, (kind, i)
+    band = ["-b", str(WP.READ_SET_BAND["extra_b"]), "-f", str(WP.READ_SET_BAND["extra_f"])]
+    for opts, kw in ((["-O", "4,0", "-E", "2"], T.AFFINE), (["-O", "4,0", "-E", "2"] + band, dict(T.AFFINE, **WP.READ_SET_BAND)), (band, dict(WP.CONVEX, **WP.READ_SET_BAND))):
+        for i, reads in enumerate(sets):
+            reads = list(reads)
+            fa = str(tmp_path / f"{kind}{i}.fa")
+            synth.write_fasta(fa, reads)
+            ref = subprocess.run([os.path.join(H.REF_DIR, "abpoa_ref")] + opts + ["-r", "2", fa], capture_output=True, text=True, check=True, timeout=300)
+            r = api.msa_batch([reads], api.Params(**kw), out_cons=True, out_msa=True, lib=H.cpu_shim_lib(), n_threads=2)[0]
+            assert r.status == 0
+            assert api.format_output(r, [f"r{j}" for j in range(len(reads))], True, True) == ref.stdout, (kind, i, opts)
 
 
 @pytest.mark.skipif(not H.have_ref(), reason="reference build not available")
