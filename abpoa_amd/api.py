@@ -11,12 +11,43 @@ from . import ffi, seqio
 
 GLOBAL, LOCAL, EXTEND = 0, 1, 2
 LINEAR, AFFINE, CONVEX = 0, 1, 2
-OUT_CONS, OUT_MSA, AMB_STRAND = 1, 2, 4
+OUT_CONS, OUT_MSA, AMB_STRAND, PROGRESSIVE = 1, 2, 4, 8
+GUIDE_HITS, GUIDE_SKETCH = 0x01000000, 0x02000000
+
+
+def guide_kw(k=0, w=0):
+    """ABPOA_HIP_GUIDE_KW: the sketch's k-mer size in flag bits 8-15, its window in bits 16-23 (0: the reference's default)."""
+    if not (0 <= int(k) <= 255 and 0 <= int(w) <= 255):
+        raise ValueError("guide order: k and w are 8-bit fields (valid: k 1..28, amino acids 1..11; w 1..255; 0 = default)")
+    return int(k) << 8 | int(w) << 16
+
+
+def check_guide_kw(k, w, is_aa=False):
+    """What the library accepts (abpoa_hip_msa_batch returns ABPOA_HIP_EINVAL for the rest): k 0 or 1..28 (amino acids 1..11), w 0 or 1..255."""
+    if not (k == 0 or 1 <= k <= (11 if is_aa else 28)) or not (0 <= w <= 255):
+        raise ValueError(f"guide order: k = {k}, w = {w} outside k 1..{11 if is_aa else 28}, w 1..255")
+    return guide_kw(k, w)
+
+
+def _batch_flags(params, out_cons, out_msa, amb_strand, progressive, mm_k, mm_w):
+    flags = (OUT_CONS if out_cons else 0) | (OUT_MSA if out_msa else 0) | (AMB_STRAND if amb_strand else 0)
+    if progressive:
+        flags |= PROGRESSIVE | check_guide_kw(mm_k, mm_w, params.m > 5)
+    return flags
 
 
 class ReadSet(C.Structure):          # abpoa_hip_readset_t
     _fields_ = [("n_reads", C.c_int32), ("seqs", C.POINTER(C.POINTER(C.c_uint8))), ("lens", C.POINTER(C.c_int32)),
                 ("weights", C.POINTER(C.POINTER(C.c_int32)))]
+
+
+class Guide(C.Structure):            # abpoa_hip_guide_t
+    _fields_ = [("status", C.c_int32), ("n_reads", C.c_int32), ("order", C.POINTER(C.c_int32)), ("hit", C.POINTER(C.c_int32)),
+                ("mm_off", C.POINTER(C.c_int64)), ("mm", C.POINTER(C.c_uint64))]
+
+
+class GuideTiming(C.Structure):      # abpoa_hip_guide_timing_t
+    _fields_ = [("sketch_ms", C.c_double), ("pair_ms", C.c_double), ("total_s", C.c_double), ("n_minimizers", C.c_int64)]
 
 
 class Msa(C.Structure):              # abpoa_hip_msa_t
@@ -180,16 +211,18 @@ class EncodedSets:
             self.sets[i] = ReadSet(len(rs), ptrs, lens, wptrs)
 
 
-def msa_batch(read_sets, params, out_cons=True, out_msa=False, n_threads=0, lib=None, encoded=None, weights=None, amb_strand=False):
+def msa_batch(read_sets, params, out_cons=True, out_msa=False, n_threads=0, lib=None, encoded=None, weights=None, amb_strand=False,
+              progressive=False, mm_k=0, mm_w=0):
     """Consensus / MSA of many independent read-sets (lists of strings) in one call.
     Returns a list of SetResult.  `lib` defaults to the HIP engine (tests may pass the CPU shim).
-    weights: per set, per read, per base edge weights (the reference's -Q); amb_strand: the reference's -s."""
+    weights: per set, per read, per base edge weights (the reference's -Q); amb_strand: the reference's -s;
+    progressive: the reference's -p, reads aligned in guide-tree order (mm_k / mm_w: its -k / -w, 0 = default)."""
     lib = lib or ffi.lib()
     _bind_msa(lib)
     enc = encoded or EncodedSets(read_sets, params.m, weights)
     out = (Msa * enc.n)()
     sc = params.scoring()
-    flags = (OUT_CONS if out_cons else 0) | (OUT_MSA if out_msa else 0) | (AMB_STRAND if amb_strand else 0)
+    flags = _batch_flags(params, out_cons, out_msa, amb_strand, progressive, mm_k, mm_w)
     rc = lib.abpoa_hip_msa_batch(C.byref(sc), enc.n, enc.sets, out, flags, n_threads)
     if rc != 0:
         raise ffi.EngineError(f"abpoa_hip_msa_batch failed ({rc}): {lib.abpoa_hip_last_error().decode() if hasattr(lib, 'abpoa_hip_last_error') else ''}")
@@ -222,11 +255,12 @@ class BatchContext:
 
     __del__ = close
 
-    def msa_batch(self, read_sets, params, out_cons=True, out_msa=False, n_threads=0, encoded=None, weights=None):
+    def msa_batch(self, read_sets, params, out_cons=True, out_msa=False, n_threads=0, encoded=None, weights=None, amb_strand=False, progressive=False,
+                  mm_k=0, mm_w=0):
         enc = encoded or EncodedSets(read_sets, params.m, weights)
         out = (Msa * enc.n)()
         sc = params.scoring()
-        flags = (OUT_CONS if out_cons else 0) | (OUT_MSA if out_msa else 0)
+        flags = _batch_flags(params, out_cons, out_msa, amb_strand, progressive, mm_k, mm_w)
         rc = self.lib.abpoa_hip_msa_batch_ctx(self.h, C.byref(sc), enc.n, enc.sets, out, flags, n_threads)
         if rc != 0:
             raise ffi.EngineError(f"abpoa_hip_msa_batch_ctx failed ({rc}): {self.lib.abpoa_hip_ctx_last_error(self.h).decode()}")
@@ -246,6 +280,56 @@ def msa_timing(lib=None):
     d = {k: getattr(t, k) for k, _ in MsaTiming._fields_}
     d["pad"] = d["n_host_sets"]          # (the field's name before round 4)
     return d
+
+
+class GuideOrder:
+    """The pre-pass's result for one read-set: order[r] = read aligned in round r; hit = the triangular matrix as a list (or None);
+    sketch = per read the ascending minimizer values as numpy uint64 arrays (or None)."""
+    __slots__ = ("order", "hit", "sketch")
+
+    def __init__(self, order, hit, sketch):
+        self.order, self.hit, self.sketch = order, hit, sketch
+
+
+def guide_order(read_sets, params, mm_k=0, mm_w=0, both_strands=False, hits=False, sketch=False, lib=None, encoded=None):
+    """abpoa_hip_guide_order: the guide-tree order (-p) of every read-set alone, computed by the device pre-pass."""
+    lib = lib or ffi.lib()
+    lib.abpoa_hip_guide_order.argtypes = [C.POINTER(ffi.Scoring), C.c_int, C.POINTER(ReadSet), C.c_uint, C.POINTER(Guide)]
+    lib.abpoa_hip_guide_order.restype = C.c_int
+    lib.abpoa_hip_free_guide.argtypes = [C.POINTER(Guide), C.c_int]
+    lib.abpoa_hip_free_guide.restype = None
+    enc = encoded or EncodedSets(read_sets, params.m)
+    out = (Guide * enc.n)()
+    sc = params.scoring()
+    flags = check_guide_kw(mm_k, mm_w, params.m > 5) | (AMB_STRAND if both_strands else 0) | (GUIDE_HITS if hits else 0) | (GUIDE_SKETCH if sketch else 0)
+    rc = lib.abpoa_hip_guide_order(C.byref(sc), enc.n, enc.sets, flags, out)
+    if rc != 0:
+        raise ffi.EngineError(f"abpoa_hip_guide_order failed ({rc}): {lib.abpoa_hip_last_error().decode()}")
+    try:
+        res = []
+        for i in range(enc.n):
+            o, n = out[i], out[i].n_reads
+            order = [o.order[r] for r in range(n)]
+            hit = np.ctypeslib.as_array(o.hit, (n * (n + 1) // 2,)).tolist() if hits and n else ([] if hits else None)
+            sk = None
+            if sketch:
+                off = [o.mm_off[r] for r in range(n + 1)]
+                vals = np.ctypeslib.as_array(o.mm, (max(1, off[-1]),)).copy()
+                sk = [vals[off[r]:off[r + 1]] for r in range(n)]
+            res.append(GuideOrder(order, hit, sk))
+        return res
+    finally:
+        lib.abpoa_hip_free_guide(out, enc.n)
+
+
+def guide_timing(lib=None):
+    """Kernel durations (ms), wall time (s) and minimizer count of the last guide-order pre-pass."""
+    lib = lib or ffi.lib()
+    t = GuideTiming()
+    lib.abpoa_hip_get_guide_timing.argtypes = [C.POINTER(GuideTiming)]
+    lib.abpoa_hip_get_guide_timing.restype = None
+    lib.abpoa_hip_get_guide_timing(C.byref(t))
+    return {k: getattr(t, k) for k, _ in GuideTiming._fields_}
 
 
 HOST_REASONS = ["other", "node slots at the first read", "predecessor-list slots", "cigar slots", "node slots while fusing", "edge / aligned slots of a node",

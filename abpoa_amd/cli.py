@@ -7,10 +7,12 @@
   -c amino-acid input   -l input is a LIST of sequence files (one read-set each)   -o FILE output [stdout]
   -r INT  0 consensus FASTA, 1 MSA (PIR), 2 both
   -s  ambiguous strand: a read that aligns badly is tried as its reverse complement    -Q  FASTQ qualities as edge weights
+  -p  progressive: align the reads of a set in the order of the guide tree built from their minimizers (global mode; no seeding)
+  -k INT / -w INT  minimizer k-mer size / window of that guide tree [19 / 10; amino acids 7 / 4]
 
 With -l every file of the list is one read-set and ALL of them go through ONE abpoa_hip_msa_batch call (the reference
 loops over the files one at a time, src/abpoa.c:128-135); the output is the concatenation the reference prints.
-Options outside the engine (-S -p -i -d -g, -r 3/4/5) exit with an error rather than being ignored."""
+Options outside the engine (-S -i -d -g, -r 3/4/5) exit with an error rather than being ignored."""
 import argparse
 import sys
 
@@ -41,6 +43,9 @@ def build_parser():
     ap.add_argument("-r", "--result", type=int, default=0)
     ap.add_argument("-s", "--amb-strand", action="store_true")
     ap.add_argument("-Q", "--use-qual-weight", action="store_true")
+    ap.add_argument("-p", "--progressive", action="store_true")
+    ap.add_argument("-k", "--k-mer", type=int, default=0)       # (0: the reference's default for the alphabet)
+    ap.add_argument("-w", "--window", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0)
     return ap
 
@@ -50,6 +55,12 @@ def main(argv=None, lib=None, out=None):
     if a.result not in (0, 1, 2, 5):
         sys.stderr.write("abpoa_amd: -r %d (GFA output) is outside this engine\n" % a.result)
         return 2
+    if a.progressive:
+        try:
+            api.check_guide_kw(a.k_mer, a.window, a.amino_acid)
+        except ValueError as e:
+            sys.stderr.write("abpoa_amd: %s\n" % e)
+            return 2
     o1, o2 = _pair(a.gap_open, 24)
     e1, e2 = _pair(a.gap_ext, 1)
     params = api.Params(aln_mode=a.aln_mode, is_aa=a.amino_acid, match=a.match, mismatch=a.mismatch, score_matrix=a.matrix,
@@ -69,7 +80,8 @@ def main(argv=None, lib=None, out=None):
         weights.append([seqio.qv_weights(x, y) for x, y in zip(s, q)])
     out_cons, out_msa, out_fq = a.result in (0, 2, 5), a.result in (1, 2), a.result == 5
     res = api.msa_batch(sets, params, out_cons=out_cons, out_msa=out_msa, n_threads=a.threads, lib=lib,
-                        weights=weights if a.use_qual_weight else None, amb_strand=a.amb_strand)
+                        weights=weights if a.use_qual_weight else None, amb_strand=a.amb_strand,
+                        progressive=a.progressive, mm_k=a.k_mer, mm_w=a.window)
     sink = out or (open(a.output, "w") if a.output else sys.stdout)
     try:
         for n, r in zip(names, res):

@@ -10,6 +10,7 @@
 #include "msa_batch.h"
 #include "msa_device.h"
 #include "msa_passes.h"
+#include "guide_order.h"
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -252,17 +253,113 @@ int msa_batch_impl(const abpoa_hip_scoring_t *sc_in, int n_sets, const abpoa_hip
     if (rc_host != ABPOA_HIP_OK) free_all(out, n_sets);
     return rc_host;
 }
+
+// ---- guide-tree read order (ABPOA_HIP_PROGRESSIVE, the reference's -p): the device pre-pass orders the reads of every set, the drivers above run on a
+// view of the sets in that order, and the MSA rows go back to input order.  Only the pointer arrays are permuted, no base is copied.
+static_assert(GUIDE_QUEUES == MSA_DEVICE_SLOTS, "one pre-pass queue per device queue");
+abpoa_hip_guide_timing_t g_guide_timing; std::mutex g_guide_timing_mu;
+struct PermutedSets {
+    std::vector<abpoa_hip_readset_t> sets;
+    std::vector<std::vector<const uint8_t *>> seqs; std::vector<std::vector<int32_t>> lens; std::vector<std::vector<const int32_t *>> weights;
+    PermutedSets(int n_sets, const abpoa_hip_readset_t *in, const GuideResult &G) : sets(n_sets), seqs(n_sets), lens(n_sets), weights(n_sets) {
+        for (int s = 0; s < n_sets; ++s) {
+            const int n = in[s].n_reads; const int32_t *order = G.order.data() + G.set_read0[s];
+            seqs[s].resize(n); lens[s].resize(n); if (in[s].weights) weights[s].resize(n);
+            for (int r = 0; r < n; ++r) { seqs[s][r] = in[s].seqs[order[r]]; lens[s][r] = in[s].lens[order[r]]; if (in[s].weights) weights[s][r] = in[s].weights[order[r]]; }
+            sets[s].n_reads = n; sets[s].seqs = seqs[s].data(); sets[s].lens = lens[s].data(); sets[s].weights = in[s].weights ? weights[s].data() : nullptr;
+        }
+    }
+};
+// MSA row r of the ordered run is input read order[r]: row order[r] of what the caller gets; the consensus row stays last
+int rows_to_input_order(abpoa_hip_msa_t &o, const int32_t *order) {
+    if (o.status != ABPOA_HIP_OK || !o.msa_base || o.msa_len <= 0 || o.msa_rows < o.n_reads) return ABPOA_HIP_OK;
+    const size_t len = (size_t)o.msa_len;
+    uint8_t *rows = (uint8_t *)malloc((size_t)o.msa_rows * len);
+    if (!rows) return ABPOA_HIP_ENOMEM;
+    memcpy(rows, o.msa_base, (size_t)o.msa_rows * len);
+    for (int r = 0; r < o.n_reads; ++r) memcpy(rows + (size_t)order[r] * len, o.msa_base + (size_t)r * len, len);
+    free(o.msa_base); o.msa_base = rows;
+    return ABPOA_HIP_OK;
+}
+void note_guide_timing(const GuideResult &G) {
+    std::lock_guard<std::mutex> lk(g_guide_timing_mu);
+    g_guide_timing.sketch_ms = G.sketch_ms; g_guide_timing.pair_ms = G.pair_ms; g_guide_timing.total_s = G.total_s;
+    g_guide_timing.n_minimizers = G.mm_off.empty() ? 0 : G.mm_off.back();
+}
+
+// The batch entry with the flags of include/abpoa_hip.h: without ABPOA_HIP_PROGRESSIVE, and with it outside global mode (reference abpoa_align.c:408),
+// msa_batch_impl as it is.
+int msa_batch_entry(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, abpoa_hip_msa_t *out, unsigned flags,
+                    int n_threads, abpoa_hip_msa_timing_t &tm, int ctx_device, int ctx_slot) {
+    if (!(flags & ABPOA_HIP_PROGRESSIVE)) return msa_batch_impl(sc, n_sets, sets, out, flags & ~ABPOA_HIP_GUIDE_KW(0xff, 0xff), n_threads, tm, ctx_device, ctx_slot);      // (k / w mean nothing without the flag)
+    const unsigned plain = flags & (ABPOA_HIP_OUT_CONS | ABPOA_HIP_OUT_MSA | ABPOA_HIP_AMB_STRAND);
+    GuideParams gp;
+    if (!sc || guide_params(sc->m, flags, &gp) != ABPOA_HIP_OK) { set_err("guide order: k-mer size / window outside 1..28 (amino acids 1..11) / 1..255"); return ABPOA_HIP_EINVAL; }
+    if (sc->align_mode != ABPOA_HIP_GLOBAL_MODE || n_sets <= 0 || !sets || !out) return msa_batch_impl(sc, n_sets, sets, out, plain, n_threads, tm, ctx_device, ctx_slot);
+    if (engine_device() < 0) { const int rc = abpoa_hip_init(ctx_device >= 0 ? ctx_device : 0); if (rc) return rc; }
+    if (const int rc = validate_sets(n_sets, sets)) return rc;
+    GuideResult G;
+    if (const int rc = guide_prepass(gp, n_sets, sets, ctx_device, ctx_slot >= 0 ? ctx_slot : 0, false, G)) return rc;
+    note_guide_timing(G);
+    const PermutedSets P(n_sets, sets, G);
+    // no strand retry under a guide order (the reference aligns every read forward there, abpoa_align.c:248-250): -s only chose the sketch's strands
+    const int rc = msa_batch_impl(sc, n_sets, P.sets.data(), out, plain & ~ABPOA_HIP_AMB_STRAND, n_threads, tm, ctx_device, ctx_slot);
+    if (rc != ABPOA_HIP_OK) return rc;
+    for (int s = 0; s < n_sets; ++s) {
+        int rc_s = rows_to_input_order(out[s], G.order.data() + G.set_read0[s]);
+        if (rc_s == ABPOA_HIP_OK && (flags & ABPOA_HIP_AMB_STRAND) && !out[s].is_rc && !(out[s].is_rc = (uint8_t *)calloc((size_t)std::max(1, sets[s].n_reads), 1))) rc_s = ABPOA_HIP_ENOMEM;
+        if (rc_s != ABPOA_HIP_OK) { free_all(out, n_sets); return rc_s; }
+    }
+    return ABPOA_HIP_OK;
+}
 }  // namespace
 }  // namespace abpoa_hip
 
 extern "C" {
+int abpoa_hip_guide_order(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, unsigned flags, abpoa_hip_guide_t *out) {
+    using namespace abpoa_hip;
+    refresh_options();
+    GuideParams gp;
+    if (!sc || n_sets < 0 || (n_sets > 0 && (!sets || !out))) return ABPOA_HIP_EINVAL;
+    if (guide_params(sc->m, flags, &gp) != ABPOA_HIP_OK) { set_err("guide order: k-mer size / window outside 1..28 (amino acids 1..11) / 1..255"); return ABPOA_HIP_EINVAL; }
+    if (engine_device() < 0) { const int rc = abpoa_hip_init(0); if (rc) return rc; }
+    if (const int rc = validate_sets(n_sets, sets)) return rc;
+    GuideResult G;
+    if (const int rc = guide_prepass(gp, n_sets, sets, -1, 0, flags & ABPOA_HIP_GUIDE_SKETCH, G)) return rc;
+    note_guide_timing(G);
+    for (int s = 0; s < n_sets; ++s) memset(&out[s], 0, sizeof(out[s]));
+    for (int s = 0; s < n_sets; ++s) {
+        abpoa_hip_guide_t &o = out[s];
+        const int64_t n = sets[s].n_reads, r0 = G.set_read0[s], n_hit = n * (n + 1) / 2, m0 = G.mm_off[r0], n_mm = G.mm_off[r0 + n] - m0;
+        o.n_reads = (int32_t)n;
+        o.order = (int32_t *)malloc(sizeof(int32_t) * (size_t)std::max<int64_t>(1, n));
+        bool ok = o.order != nullptr;
+        if (ok) memcpy(o.order, G.order.data() + r0, sizeof(int32_t) * (size_t)n);
+        if (ok && (flags & ABPOA_HIP_GUIDE_HITS)) {
+            ok = (o.hit = (int32_t *)malloc(sizeof(int32_t) * (size_t)std::max<int64_t>(1, n_hit))) != nullptr;
+            if (ok) memcpy(o.hit, G.hit.data() + G.set_hit0[s], sizeof(int32_t) * (size_t)n_hit);
+        }
+        if (ok && (flags & ABPOA_HIP_GUIDE_SKETCH)) {
+            o.mm_off = (int64_t *)malloc(sizeof(int64_t) * (size_t)(n + 1)); o.mm = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)std::max<int64_t>(1, n_mm));
+            ok = o.mm_off && o.mm;
+            if (ok) { for (int64_t r = 0; r <= n; ++r) o.mm_off[r] = G.mm_off[r0 + r] - m0; memcpy(o.mm, G.mm.data() + m0, sizeof(uint64_t) * (size_t)n_mm); }
+        }
+        if (!ok) { abpoa_hip_free_guide(out, n_sets); set_err("guide order: host memory for the results"); return ABPOA_HIP_ENOMEM; }
+    }
+    return ABPOA_HIP_OK;
+}
+void abpoa_hip_free_guide(abpoa_hip_guide_t *r, int n) {
+    for (int i = 0; r && i < n; ++i) { free(r[i].order); free(r[i].hit); free(r[i].mm_off); free(r[i].mm); memset(&r[i], 0, sizeof(r[i])); }
+}
+void abpoa_hip_get_guide_timing(abpoa_hip_guide_timing_t *out) { std::lock_guard<std::mutex> lk(abpoa_hip::g_guide_timing_mu); if (out) *out = abpoa_hip::g_guide_timing; }
+int abpoa_hip_guide_tile(void) { return abpoa_hip::guide_tile_length(); }
 void abpoa_hip_get_host_reasons(int32_t *out12) {
     std::lock_guard<std::mutex> lk(abpoa_hip::g_reason_mu);
     for (int i = 0; i < abpoa_hip::MSA_HOST_REASONS; ++i) out12[i] = abpoa_hip::g_host_reasons[i];
 }
 int abpoa_hip_msa_batch(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, abpoa_hip_msa_t *out, unsigned flags, int n_threads) {
     abpoa_hip::refresh_options();
-    return abpoa_hip::msa_batch_impl(sc, n_sets, sets, out, flags, n_threads, abpoa_hip::g_timing, -1, -1);
+    return abpoa_hip::msa_batch_entry(sc, n_sets, sets, out, flags, n_threads, abpoa_hip::g_timing, -1, -1);
 }
 void abpoa_hip_get_msa_timing(abpoa_hip_msa_timing_t *out) { *out = abpoa_hip::g_timing; }
 // ---- contexts
@@ -290,11 +387,11 @@ int abpoa_hip_msa_batch_ctx(abpoa_hip_ctx_t *c, const abpoa_hip_scoring_t *sc, i
     abpoa_hip::refresh_options();
     if (!c) return ABPOA_HIP_EINVAL;
     abpoa_hip::clear_thread_error();
-    const int rc = abpoa_hip::msa_batch_impl(sc, n_sets, sets, out, flags, n_threads, c->timing, c->device, c->slot);
+    const int rc = abpoa_hip::msa_batch_entry(sc, n_sets, sets, out, flags, n_threads, c->timing, c->device, c->slot);
     if (rc != ABPOA_HIP_OK) { const char *m = abpoa_hip::thread_last_error(); snprintf(c->err, sizeof(c->err), "%s", m[0] ? m : abpoa_hip_last_error()); } else c->err[0] = 0;
     return rc;
 }
 void abpoa_hip_ctx_get_msa_timing(const abpoa_hip_ctx_t *c, abpoa_hip_msa_timing_t *out) { if (c && out) *out = c->timing; }
 const char *abpoa_hip_ctx_last_error(const abpoa_hip_ctx_t *c) { return c ? c->err : "null context"; }
-void abpoa_hip_trim(void) { abpoa_hip::release_msa_device_caches(); }
+void abpoa_hip_trim(void) { abpoa_hip::release_msa_device_caches(); abpoa_hip::release_guide_queues(); }
 }

@@ -92,7 +92,9 @@ class msa_aligner:
         r = api.msa_batch([list(seqs)], self.params, out_cons=bool(out_cons), out_msa=bool(out_msa), lib=self._lib)[0]
         return self._wrap(seqs, r, out_cons, out_msa)
 
-    def msa_batch(self, read_sets, out_cons=True, out_msa=False, n_threads=0):
-        """Many independent read-sets (lists of sequences) in one engine call -> list of msa_result."""
-        rs = api.msa_batch([list(s) for s in read_sets], self.params, out_cons=bool(out_cons), out_msa=bool(out_msa), n_threads=n_threads, lib=self._lib)
+    def msa_batch(self, read_sets, out_cons=True, out_msa=False, n_threads=0, progressive=False):
+        """Many independent read-sets (lists of sequences) in one engine call -> list of msa_result.
+        progressive: the reads of every set in guide-tree order (abpoa -p; msa() keeps the reference binding's signature, which forces it off)."""
+        rs = api.msa_batch([list(s) for s in read_sets], self.params, out_cons=bool(out_cons), out_msa=bool(out_msa), n_threads=n_threads, lib=self._lib,
+                           progressive=bool(progressive))
         return [self._wrap(s, r, out_cons, out_msa) for s, r in zip(read_sets, rs)]

@@ -167,7 +167,7 @@ int  abpoa_hip_score_bits(const abpoa_hip_scoring_t *sc, int n_rows, int qlen, i
 /* Progressive POA of N independent read-sets in lock-step rounds: round k aligns read k of every
  * set to that set's graph (one launch for all sets) and fuses the cigars into the graphs.
  * Per set this is the reference's abpoa_msa() (src/abpoa_align.c:373-437) with plain abpoa_poa()
- * (:302-344): no seeding / guide tree, unit weights, no reverse-complement retry.  Graph fusion and
+ * (:302-344), or -- with ABPOA_HIP_PROGRESSIVE -- in the order of the reference's guide tree (-p).  No seeding.  Graph fusion and
  * the consensus / MSA calls follow the reference so that outputs are identical.
  * Two drivers, same results: the DEVICE-RESIDENT driver (global mode, adaptive band, affine / convex
  * gaps, consensus output, nucleotides) keeps every graph in HBM and runs fusion, row order, band
@@ -201,6 +201,37 @@ typedef struct abpoa_hip_msa_t {
 #define ABPOA_HIP_OUT_MSA  0x2u   /* abpoa_para_t.out_msa  */
 #define ABPOA_HIP_AMB_STRAND 0x4u /* abpoa_para_t.amb_strand (-s): a read whose best score is below min(qlen, nodes - 2) * max_mat / 3 is aligned
                                      again as its reverse complement and the better strand goes into the graph (src/abpoa_align.c:315-336) */
+
+/* abpoa_para_t.progressive_poa (-p): the reads of every set are aligned in the order of the reference's guide tree (src/abpoa_seed.c:231-324) -- the most
+ * similar pair first, then always the read most similar to those already in the graph, similarity = Jaccard index of the reads' minimizer sketches.
+ * A device pre-pass (sketch kernel, pair kernel) builds the order for all sets of the call; MSA row i stays input read i.  Global mode only: in local
+ * and extension mode the flag changes nothing (src/abpoa_align.c:408); sets of fewer than 3 reads and sets without any minimizer keep the input order.
+ * Under this flag no read is retried as its reverse complement (the reference aligns every read forward there, :248-250): ABPOA_HIP_AMB_STRAND then only
+ * makes the sketch take the smaller strand of every k-mer, and is_rc comes back all zero.  Honoured by abpoa_hip_msa_batch and abpoa_hip_msa_batch_ctx. */
+#define ABPOA_HIP_PROGRESSIVE 0x8u
+/* k-mer size (flag bits 8-15) and window (bits 16-23) of the sketch, abpoa_para_t.k / .w (-k / -w); 0 = the reference's defaults k = 19, w = 10, for
+ * amino acids k = 7, w = 4.  Valid: k 1..28 (amino acids 1..11), w 1..255; anything else returns ABPOA_HIP_EINVAL. */
+#define ABPOA_HIP_GUIDE_KW(k, w) ((((unsigned)(k)) & 0xffu) << 8 | (((unsigned)(w)) & 0xffu) << 16)
+
+/* The pre-pass alone: out[s].order[r] = the read of set s aligned in round r.  flags: ABPOA_HIP_GUIDE_KW, ABPOA_HIP_AMB_STRAND (both strands) and what
+ * else to return.  The order is built whatever sc->align_mode says.  Release out[0..n_sets) with abpoa_hip_free_guide. */
+#define ABPOA_HIP_GUIDE_HITS   0x01000000u   /* also the triangular hit matrix                                 */
+#define ABPOA_HIP_GUIDE_SKETCH 0x02000000u   /* also the sketch values of every read                           */
+typedef struct abpoa_hip_guide_t {
+    int32_t   status;             /* ABPOA_HIP_OK                                                               */
+    int32_t   n_reads;
+    int32_t  *order;              /* [n_reads]                                                                  */
+    int32_t  *hit;                /* NULL, or [n_reads*(n_reads+1)/2]: hit[i*(i+1)/2+j], j <= i (mm_hit_n, src/abpoa_seed.c:239-243) */
+    int64_t  *mm_off;             /* NULL, or [n_reads+1]: read r owns mm[mm_off[r] .. mm_off[r+1])              */
+    uint64_t *mm;                 /* hash64(k-mer) << 8 | k of every minimizer the reference's sketch emits, ascending per read */
+} abpoa_hip_guide_t;
+int  abpoa_hip_guide_order(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, unsigned flags, abpoa_hip_guide_t *out);
+void abpoa_hip_free_guide(abpoa_hip_guide_t *r, int n);
+/* The pre-pass of the last call that ran one (process-wide): kernel durations by hipEvents on its queue, its wall time, minimizers found. */
+typedef struct abpoa_hip_guide_timing_t { double sketch_ms, pair_ms, total_s; int64_t n_minimizers; } abpoa_hip_guide_timing_t;
+void abpoa_hip_get_guide_timing(abpoa_hip_guide_timing_t *out);
+/* Positions per tile of the sketch kernel: reads longer than this cross a tile edge, where the walk's state is carried (usable without a GPU). */
+int  abpoa_hip_guide_tile(void);
 
 /* n_threads <= 0: one host thread per online core.  Every out[i] must be released with
  * abpoa_hip_free_msa.  Fails with ABPOA_HIP_ENODEV when no GPU is usable. */
