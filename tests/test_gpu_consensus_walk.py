@@ -3,18 +3,14 @@ that run three 64-row blocks ahead, the pointer jumping over rows with one heavi
 
 Every set is compared with the CPU build of the host layer whose aligner is the plain-C oracle (tests/cpu_shim.cpp): status, consensus, per-base coverage.
 Every job also runs under ABPOA_HIP_DEVSYNC=1, where the library recomputes the consensus of a job's first four sets on the host from the downloaded graph
-(DeviceDebug::consensus_check) -- so no job has more than four sets.  ONE child process runs every job in both forms and reports."""
-import json
-import os
-import subprocess
-import sys
-
+(DeviceDebug::consensus_check) -- so no job has more than four sets.  ONE child process (tests/readset_worker.py) runs every job of make_jobs() in both forms
+and reports."""
 import numpy as np
 import pytest
 
+from readset_worker import run_report
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 AFFINE = dict(gap_open1=4, gap_open2=0, gap_ext1=2)
 NT = "ACGT"
@@ -66,10 +62,14 @@ def _ragged_set(seed, n_reads, span):
     return [t] + [_substituted(rng, t[7 * i + 3:len(t) - (span - 7 * i)], 0.01) for i in range(1, n_reads)]
 
 
+FORMS = {"default": {}, "devsync": {"ABPOA_HIP_DEVSYNC": "1", "ABPOA_HIP_HOSTGRAPH": "0"}}
+
+
 def make_jobs():
+    """{job: spec} for tests/readset_worker.py."""
     from abpoa_amd import synth, workloads
     rng = np.random.default_rng(16)
-    return {
+    table = {
         # graphs of 63, 64, 65 and of 127, 128, 129 rows: the sink is the last row of a block, the first of the next, and one further
         "rows_63_65": (AFFINE, _chain_sets((61, 62, 63), 1)),
         "rows_127_129": (AFFINE, _chain_sets((125, 126, 127), 2)),
@@ -81,50 +81,14 @@ def make_jobs():
         "protein": (dict(is_aa=True, score_matrix=workloads.BLOSUM62), [synth.make_read_set(75, i, 6, 90 + 45 * i, alphabet=synth.AA, rates=(0.06, 0.03, 0.03)) for i in range(3)]),
         "degenerate": (AFFINE, [[_template(rng, 150)], [], synth.make_read_set(77, 0, 5, 100, 0.05), [_template(rng, 1)]]),
     }
-
-
-WORKER = r"""
-import json, os, sys
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, 'tests'))
-import helpers as H
-from abpoa_amd import api, ffi
-import test_gpu_consensus_walk as T
-def record(res):
-    return dict(status=[r.status for r in res], cons=[r.cons_seq for r in res], cov=[list(map(int, r.cons_cov)) for r in res])
-lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0)); shim = H.cpu_shim_lib()
-report = {}
-for job, (kw, sets) in T.make_jobs().items():
-    p = api.Params(**kw)
-    rep = {}
-    for form, env in (('default', {}), ('devsync', {'ABPOA_HIP_DEVSYNC': '1', 'ABPOA_HIP_HOSTGRAPH': '0'})):
-        os.environ.update(env)
-        sys.stderr.write('[job] %%s %%s\n' %% (job, form)); sys.stderr.flush()
-        rep[form] = record(api.msa_batch(sets, p, n_threads=4))
-        rep[form]['n_host_sets'] = int(api.msa_timing()['n_host_sets'])
-        for k in env: del os.environ[k]
-    ref = api.msa_batch(sets, p, out_cons=True, out_msa=True, n_threads=4, lib=shim)
-    rep['oracle'] = record(ref)
-    rep['oracle']['msa'] = [r.msa_seq for r in ref]
-    report[job] = rep
-print('REPORT ' + json.dumps(report))
-"""
+    return {job: dict(params=kw, sets=sets, forms=FORMS, record=("n_host_sets",), ref_record=("msa",)) for job, (kw, sets) in table.items()}
 
 
 @pytest.fixture(scope="module")
 def report():
-    env = dict(os.environ)
-    for k in ("ABPOA_HIP_DEVSYNC", "ABPOA_HIP_HOSTGRAPH", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_DBG"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", WORKER % dict(root=ROOT)], capture_output=True, text=True, env=env, timeout=600)
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("REPORT ")]
-    assert r.returncode == 0 and lines, (r.stdout[-1500:], r.stderr[-3000:])
-    log, key = {}, None      # (job, form) -> what the library said on stderr during that run
-    for ln in r.stderr.splitlines():
-        if ln.startswith("[job] "):
-            key = tuple(ln.split()[1:3]); log[key] = []
-        elif key:
-            log[key].append(ln)
-    return json.loads(lines[0][7:]), {k: "\n".join(v) for k, v in log.items()}
+    """(the report, {(job, form): what the library said on stderr during that run})"""
+    return run_report("test_gpu_consensus_walk", set_env={}, timeout=600, want_log=True,
+                      clear_env=("ABPOA_HIP_DEVSYNC", "ABPOA_HIP_HOSTGRAPH", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_DBG"))
 
 
 JOBS = ["rows_63_65", "rows_127_129", "skip_blocks", "ties", "ties_convex", "ragged", "protein", "degenerate"]
@@ -138,7 +102,7 @@ def test_the_job_list_is_the_workers():
 def test_consensus_equals_the_oracle_backed_run(report, job):
     rep, log = report
     r = rep[job]
-    ref = r["oracle"]
+    ref = r["ref"]
     assert all(s == 0 for s in ref["status"])
     for form in ("default", "devsync"):
         got = r[form]
@@ -153,7 +117,7 @@ def test_host_recomputation_from_the_device_graph(report, job):
     """ABPOA_HIP_DEVSYNC=1: node ids, bases and coverage of every set's consensus equal the host routine's on the downloaded graph"""
     rep, log = report
     text = log[(job, "devsync")]
-    n_sets = len(rep[job]["oracle"]["status"])
+    n_sets = len(rep[job]["ref"]["status"])
     assert "FAILED" not in text, text[-3000:]
     assert text.count("consensus check ok") == n_sets, text[-3000:]
 
@@ -163,12 +127,12 @@ def test_the_sets_are_what_they_are_meant_to_be(report):
     rep, log = report
     jobs = make_jobs()
     for job, lengths in (("rows_63_65", (61, 62, 63)), ("rows_127_129", (125, 126, 127))):
-        for msa, ln in zip(rep[job]["oracle"]["msa"], lengths):
+        for msa, ln in zip(rep[job]["ref"]["msa"], lengths):
             assert len(msa[0]) == ln, f"{job}: a read added a node ({len(msa[0])} columns for a first read of {ln})"
-    for cons, reads, gap in zip(rep["skip_blocks"]["oracle"]["cons"], jobs["skip_blocks"][1], (70, 150, 70, 150)):
+    for cons, reads, gap in zip(rep["skip_blocks"]["ref"]["cons"], jobs["skip_blocks"]["sets"], (70, 150, 70, 150)):
         assert len(cons) == len(reads[0]) - gap
-    for msa, reads in zip(rep["ragged"]["oracle"]["msa"], jobs["ragged"][1]):
+    for msa, reads in zip(rep["ragged"]["ref"]["msa"], jobs["ragged"]["sets"]):
         starts = {next(i for i, c in enumerate(row) if c != "-") for row in msa[:len(reads)]}
         assert len(starts) >= 5, "the source needs more than four out-edges of weight 1"
-    deg = rep["degenerate"]["oracle"]["cons"]
-    assert deg[0] == jobs["degenerate"][1][0][0] and deg[1] == "" and len(deg[3]) == 1
+    deg = rep["degenerate"]["ref"]["cons"]
+    assert deg[0] == jobs["degenerate"]["sets"][0][0] and deg[1] == "" and len(deg[3]) == 1

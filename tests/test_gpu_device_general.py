@@ -6,18 +6,11 @@ row order (its best cell is the first row that reaches the maximum).  Every resu
 plain-C oracle (tests/cpu_shim.cpp): MSA rows byte for byte, consensus, coverage -- and `n_host_sets == 0`: nothing went through the host driver."""
 import pytest
 
+from gpu_harness import engine  # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 
 EXTEND = 2
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
 
 
 def _same(dev, ref, what):

@@ -9,6 +9,9 @@ import sys
 
 import pytest
 
+from gpu_harness import engine  # noqa: F401  (the fixture)
+from readset_worker import run_report
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -23,15 +26,6 @@ def _both(sets, params, n_threads=8):
     dev = api.msa_batch(sets, params, n_threads=n_threads)
     tm = api.msa_timing()
     return host, dev, tm
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
 
 
 @pytest.mark.parametrize("name,kw,shape", [
@@ -275,6 +269,14 @@ CIGAR_JOBS = {
 }
 
 
+def make_jobs(job):
+    """{job: spec} for tests/readset_worker.py: one of CIGAR_JOBS in the form the child's own environment selects, and through the oracle-backed host layer."""
+    from abpoa_amd import synth
+    kw, shapes = CIGAR_JOBS[job]
+    sets = [synth.make_read_set(23, i, n, ln, err) for i, (n, ln, err) in enumerate(shapes)]
+    return {job: dict(params=kw, sets=sets, forms={"device": {}}, record=("dig", "rounds_launches", "n_host_sets"), ref_record=("dig",), ref_threads=8)}
+
+
 @pytest.mark.parametrize("job,env", [("narrow_affine", {}), ("narrow_affine", {"ABPOA_HIP_LOCKSTEP": "1"}), ("narrow_convex_noisy", {}), ("narrow_convex_noisy", {"ABPOA_HIP_LOCKSTEP": "1"}),
                                      ("narrow_affine", {"ABPOA_HIP_DBG": "2048"}),
                                      ("narrow_1500", {}), ("narrow_1500", {"ABPOA_HIP_DBG": "1024"}), ("narrow_1500", {"ABPOA_HIP_DBG": "2048"}), ("narrow_1500", {"ABPOA_HIP_DEVICE_GENERAL": "1"}),
@@ -292,39 +294,14 @@ def test_device_driver_cigars_equal_the_oracle_backed_run(engine, job, env):
     covered: the all-rounds kernel, whose backtrack is shared by four wavefronts (helper cigar parts, merged at the cells where the walks meet), and the
     lock-step launches; narrow bands and 10 kb wide bands in both arena formats (score records / direction words, 8- and 4-row score ring).  The CPU build of
     the host driver, whose aligner is the plain-C oracle, folds the same function over its cigars (msa_batch.cpp): equal digests = equal cigars, word for word."""
-    import subprocess
-    import sys
-    kw, shapes = CIGAR_JOBS[job]
-    code = ("import os, sys, ctypes; sys.path.insert(0, %r); sys.path.insert(0, os.path.join(%r, 'tests'))\n"
-            "import helpers as H\n"
-            "from abpoa_amd import api, ffi, synth, seqio\n"
-            "import numpy as np\n"
-            "def digests(lib, sets, m):\n"
-            "    out = []\n"
-            "    lib.abpoa_hip__cigar_digest.restype = ctypes.c_ulonglong\n"
-            "    for s in sets:\n"
-            "        a = np.ascontiguousarray(seqio.encode(s[0], m), np.uint8)\n"
-            "        out.append(lib.abpoa_hip__cigar_digest(a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(a), 0))\n"
-            "    return out\n"
-            "kw, shapes = %r, %r\n"
-            "sets = [synth.make_read_set(23, i, n, ln, err) for i, (n, ln, err) in enumerate(shapes)]\n"
-            "p = api.Params(**kw)\n"
-            "lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0)); lib.abpoa_hip_reset_stats()\n"
-            "dev = api.msa_batch(sets, p, n_threads=4); tm = api.msa_timing()\n"
-            "assert all(r.status == 0 for r in dev) and tm['n_host_sets'] == 0, tm\n"
-            "print('ROUNDS_LAUNCHES', ffi.stats()['rounds_launches'])\n"
-            "d_dev = digests(lib, sets, p.m); lib.abpoa_hip__cigar_digest(None, 0, 1)\n"
-            "shim = H.cpu_shim_lib(); host = api.msa_batch(sets, p, lib=shim, n_threads=8)\n"
-            "d_host = digests(shim, sets, p.m); shim.abpoa_hip__cigar_digest(None, 0, 1)\n"
-            "assert all(d != 0 for d in d_dev) and d_dev == d_host, (d_dev, d_host)\n"
-            "assert [r.cons_seq for r in dev] == [r.cons_seq for r in host]\n"
-            "print('CIGARS EQUAL')\n" % (ROOT, ROOT, kw, shapes))
-    e = dict(os.environ, ABPOA_HIP_CIGAR_DIGEST="1", **env)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=e, timeout=900)
-    assert r.returncode == 0 and "CIGARS EQUAL" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
+    rep = run_report("test_gpu_device_msa", job, set_env=dict(env, ABPOA_HIP_CIGAR_DIGEST="1"), clear_env=(), timeout=900)[job]
+    dev, ref = rep["device"], rep["ref"]
+    assert all(s == 0 for s in dev["status"]) and dev["n_host_sets"] == 0, dev
+    assert all(d != 0 for d in dev["dig"]) and dev["dig"] == ref["dig"], (dev["dig"], ref["dig"])
+    assert dev["cons"] == ref["cons"]
     # (banded linear jobs: the fast row loops and the all-rounds kernel since round 5 -- H records, lane-parallel linear backtrack steps)
     narrow_all_rounds = (job.startswith("narrow") or job == "linear_banded") and "ABPOA_HIP_LOCKSTEP" not in env and "ABPOA_HIP_DEVICE_GENERAL" not in env
-    assert ("ROUNDS_LAUNCHES 0" not in r.stdout) == narrow_all_rounds, r.stdout
+    assert (dev["rounds_launches"] != 0) == narrow_all_rounds, dev["rounds_launches"]
 
 
 def test_assembly_row_loop_equals_the_compiler_loop():

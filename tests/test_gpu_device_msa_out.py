@@ -9,17 +9,10 @@ import sys
 
 import pytest
 
+from gpu_harness import engine  # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
 
 
 def _same(dev, ref, what, cons=True, msa=True):

@@ -5,6 +5,7 @@ import os
 import pytest
 
 import helpers as H
+from gpu_harness import engine  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 D = H.GOLDEN_DIR
@@ -15,11 +16,8 @@ def _golden(name):
 
 
 @pytest.fixture(scope="module", autouse=True)
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1
-    ffi.check(lib.abpoa_hip_init(0))
+def _engine(engine):
+    return engine
 
 
 def test_cli_list_mode_on_gpu(tmp_path):

@@ -13,20 +13,14 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_harness import engine  # noqa: F401  (the fixture)
+from readset_worker import run_report
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 AFFINE = dict(gap_open1=4, gap_open2=0, gap_ext1=2)
 EDGE_LENGTHS = [255, 256, 257, 1023, 1024, 1025, 2049]      # thread / wavefront (256 positions) / super-pass (1024) edges
 TINY_LENGTHS = [1, 3, 4, 5]
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
 
 
 def _seq(rng, n, alphabet="ACGT"):
@@ -237,36 +231,23 @@ def test_edge_slots_run_out_inside_the_fuse_phase(engine, monkeypatch):
         assert api.host_reasons() == expected_host_reasons, (kw, api.host_reasons())
 
 
+def make_jobs():
+    """{job: spec} for tests/readset_worker.py: reads around a super-pass, in the form the child's own environment selects."""
+    from abpoa_amd import synth
+    sets = [synth.make_read_set(29, i, 6, 1000 + 12 * i, 0.06) for i in range(5)]
+    return {"super_pass": dict(params=AFFINE, sets=sets, forms={"device": {}}, record=("dig", "rounds_launches", "n_host_sets"), ref_record=("dig",), ref_threads=8)}
+
+
 @pytest.mark.parametrize("lockstep", ["0", "1"], ids=["all_rounds_kernel", "lockstep_rounds"])
 def test_cigars_of_reads_around_a_super_pass(lockstep):
     """ABPOA_HIP_CIGAR_DIGEST=1 (as test_gpu_device_msa.py::test_device_driver_cigars_equal_the_oracle_backed_run): the fuse phase folds every graph cigar
     into a digest per read-set before it walks it; reads of 990 - 1060 bases, equal digests = equal cigars, word for word."""
-    code = (_CHILD_HEAD +
-            "def digests(lib, sets, m):\n"
-            "    out = []\n"
-            "    lib.abpoa_hip__cigar_digest.restype = ctypes.c_ulonglong\n"
-            "    for s in sets:\n"
-            "        a = np.ascontiguousarray(seqio.encode(s[0], m), np.uint8)\n"
-            "        out.append(lib.abpoa_hip__cigar_digest(a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(a), 0))\n"
-            "    return out\n"
-            "sets = [synth.make_read_set(29, i, 6, 1000 + 12 * i, 0.06) for i in range(5)]\n"
-            "p = api.Params(gap_open1=4, gap_open2=0, gap_ext1=2)\n"
-            "lib.abpoa_hip_reset_stats()\n"
-            "dev = api.msa_batch(sets, p, n_threads=4); tm = api.msa_timing()\n"
-            "assert all(r.status == 0 for r in dev) and tm['n_host_sets'] == 0, tm\n"
-            "print('ROUNDS_LAUNCHES', ffi.stats()['rounds_launches'])\n"
-            "d_dev = digests(lib, sets, p.m); lib.abpoa_hip__cigar_digest(None, 0, 1)\n"
-            "shim = H.cpu_shim_lib(); host = api.msa_batch(sets, p, lib=shim, n_threads=8)\n"
-            "d_host = digests(shim, sets, p.m); shim.abpoa_hip__cigar_digest(None, 0, 1)\n"
-            "assert all(d != 0 for d in d_dev) and d_dev == d_host, (d_dev, d_host)\n"
-            "assert [r.cons_seq for r in dev] == [r.cons_seq for r in host] and [r.cons_cov for r in dev] == [r.cons_cov for r in host]\n"
-            "print('CIGARS EQUAL')\n")
-    e = dict(os.environ, ABPOA_HIP_CIGAR_DIGEST="1", ABPOA_HIP_LOCKSTEP=lockstep)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=e, timeout=300)
-    assert r.returncode == 0 and "CIGARS EQUAL" in r.stdout, (r.stdout[-1500:], r.stderr[-3000:])
-    assert ("ROUNDS_LAUNCHES 0" not in r.stdout) == (lockstep == "0"), r.stdout
-
-
+    rep = run_report("test_gpu_fuse_batched", set_env={"ABPOA_HIP_CIGAR_DIGEST": "1", "ABPOA_HIP_LOCKSTEP": lockstep}, clear_env=(), timeout=300)["super_pass"]
+    dev, ref = rep["device"], rep["ref"]
+    assert all(s == 0 for s in dev["status"]) and dev["n_host_sets"] == 0, dev
+    assert all(d != 0 for d in dev["dig"]) and dev["dig"] == ref["dig"], (dev["dig"], ref["dig"])
+    assert dev["cons"] == ref["cons"] and dev["cov"] == ref["cov"]
+    assert (dev["rounds_launches"] != 0) == (lockstep == "0"), dev["rounds_launches"]
 def test_device_graph_node_by_node_after_every_read():
     """ABPOA_HIP_DEVSYNC=1 ABPOA_HIP_HOSTGRAPH=0 (child process): after every read the library compares the device graph with the host graph node by node --
     bases, edge lists in slot order, weights, aligned groups, read counts -- and the row order.  Reads of 257 / 1024 / 1025 bases, a 300-base insertion,

@@ -17,6 +17,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from gpu_harness import engine  # noqa: F401  (the fixture)
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden", "guide_order")
@@ -37,15 +39,6 @@ def _load(name):
 
 
 E2E = {c["name"]: c for c in json.load(open(os.path.join(GOLD, "e2e.json")))["cases"]}
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
 
 
 def _check_sets(cases):

@@ -8,8 +8,8 @@ arena and every row's chunk store that runs past its end has a neighbour to hit.
 and tests/test_oracle_vs_reference.py pins the oracle to the compiled reference at these read lengths."""
 import pytest
 
-import helpers as H
 import local_widths as LW
+from gpu_harness import engine, launch  # noqa: F401  (engine: the fixture)
 from test_local_regimes import local_case
 
 pytestmark = pytest.mark.gpu
@@ -17,25 +17,11 @@ TEAM = pytest.mark.parametrize("team", ["0", "1"], ids=["one_wavefront", "team_o
 GOLDEN = pytest.mark.parametrize("golden", LW.GOLDENS)
 
 
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1, "no HIP device: the engine has no fallback"
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
-
-
 def _launch(items, label, orders=(1,), bits=None):
     """items: [(name, FlatCase, oracle output)] in ONE launch per trace mode and order; everything against the oracle."""
     for trace in (True, False):
         for step in orders:
-            run = items[::step]
-            outs = H.run_hip([c for _, c, _ in run], want_trace=trace)
-            assert len(outs) == len(run)
-            for (name, _, o), h in zip(run, outs):
-                assert h.status == 0 and hasattr(h, "dp_beg") == trace and h.bits == (bits or 16)
-                H.compare_outs(h, o, label=f"{label} {name} trace={trace} order={step}")
+            launch(items[::step], trace, f"{label} order={step}", bits=bits or 16)
 
 
 def _widths(golden):

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import helpers as H
-from abpoa_amd import api, ffi, seqio, synth
+from abpoa_amd import api, seqio, synth
+from gpu_harness import engine  # noqa: F401  (the fixture)
 
 pytestmark = pytest.mark.gpu
 D = H.GOLDEN_DIR
@@ -16,11 +17,8 @@ AG = dict(gap_open1=4, gap_open2=0, gap_ext1=2)
 
 
 @pytest.fixture(scope="module", autouse=True)
-def engine():
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
+def _engine(engine):
+    return engine
 
 
 def _run(fa, params, out_cons=True, out_msa=False):

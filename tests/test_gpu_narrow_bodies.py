@@ -6,29 +6,15 @@ which body; tests/test_narrow_regimes.py asserts on the CPU that the rows of eve
 word plane applies.  The oracle on skip-edge graphs is not pinned to the compiled reference (no read-set produces them); the last part is the counterweight:
 read-sets at 30 % error, whose graphs grow 100 and more nodes of 5-8 predecessors by themselves, through both forms of the device-resident driver against the
 CPU build of the host layer (tests/cpu_shim.cpp, pinned to the reference's command-line tool by tests/test_host_msa.py).  Nothing here depends on timing."""
-import ctypes
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import helpers as H
 import narrow_preds as NP
+from gpu_harness import dir_counts, engine, launch, narrow_plan  # noqa: F401  (engine: the fixture)
+from readset_worker import run_report
 
 pytestmark = pytest.mark.gpu
-ROOT = H.ROOT
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1, "no HIP device: the engine has no fallback"
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
 
 
 # one launch per group of points that share every Scoring field: (golden, variant, wb, tag) -> families (`jump` and `farjump` in int32 have match scores of their
@@ -59,34 +45,11 @@ def _group(key):
     return [(f, *_case(golden, f, variant, wb)) for f in GROUPS[key]]
 
 
-def _dir_counts(lib):
-    out = (ctypes.c_longlong * 2)()
-    lib.abpoa_hip__dir_counts(out)
-    return out[0], out[1]
-
-
-def _launch(items, trace, label):
-    """One launch of [(name, case, dict, oracle)]: every alignment against the oracle -- with the trace every plane cell, band and row arg-max too."""
-    outs = H.run_hip([it[1] for it in items], want_trace=trace)
-    assert len(outs) == len(items)
-    for (name, _, _, o), h in zip(items, outs):
-        assert h.status == 0 and hasattr(h, "dp_beg") == trace, (label, name, h.status)
-        H.compare_outs(h, o, label=f"{label} {name} trace={trace}")
-    return outs
-
-
-def _plan(case, bits):
-    from abpoa_amd import ffi
-    out = (ctypes.c_int * 4)()
-    ffi.lib().abpoa_hip__narrow_plan(ctypes.byref(case.sc), case.qlen, bits, 1, out)
-    return out[0], out[1]
-
-
 @pytest.mark.parametrize("key", list(GROUPS), ids=GROUP_IDS)
 def test_records_with_trace(engine, key):
     """Score records, trace kept: bands, every plane cell, row arg-max, best cell (extension mode: the running best), cigar, result fields, band state -- every
     family x golden x band x variant; the int32, linear and extension points take the compiler's loops."""
-    _launch(_group(key), True, f"records {key}")
+    launch(_group(key), True, f"records {key}")
 
 
 @pytest.mark.parametrize("key", list(GROUPS), ids=GROUP_IDS)
@@ -98,9 +61,9 @@ def test_without_trace(engine, monkeypatch, key, loop):
     if loop == "dbg2048":
         monkeypatch.setenv("ABPOA_HIP_DBG", "2048")
     items = _group(key)
-    _dir_counts(engine)
-    _launch(items, False, f"no trace {loop} {key}")
-    walked, redone = _dir_counts(engine)
+    dir_counts(engine)
+    launch(items, False, f"no trace {loop} {key}")
+    walked, redone = dir_counts(engine)
     assert (walked, redone) == (sum(NP.words_apply(key[0], f, key[1]) for f in GROUPS[key]), 0), (key, loop, walked, redone)
 
 
@@ -154,9 +117,9 @@ def test_record_walk_without_trace(engine, monkeypatch, key):
     """ABPOA_HIP_NODIR=1 without the trace: the record walk of backtrack.h at every point -- through graphs with rows of up to 17 predecessors, which the
     walk leaves through one of their first four; behind the eighth predecessor on `jump`, over steps of 16 to 300 rows on `farjump`; no plane is walked."""
     monkeypatch.setenv("ABPOA_HIP_NODIR", "1")
-    _dir_counts(engine)
-    _launch(_group(key), False, f"records, no trace {key}")
-    assert _dir_counts(engine) == (0, 0)
+    dir_counts(engine)
+    launch(_group(key), False, f"records, no trace {key}")
+    assert dir_counts(engine) == (0, 0)
 
 
 @pytest.mark.parametrize("golden", NP.GOLDENS)
@@ -170,13 +133,13 @@ def test_small_backtrack_windows(engine, monkeypatch, golden, wc):
     if wc:
         monkeypatch.setenv("ABPOA_HIP_BT_WC", wc)
     items = [(f, *_case(golden, f, "own", None)) for f in ("far", "many", "jump", "farjump")]
-    _dir_counts(engine)
-    _launch(items, False, f"small windows, words {golden}")
-    assert _dir_counts(engine) == (len(items), 0)
+    dir_counts(engine)
+    launch(items, False, f"small windows, words {golden}")
+    assert dir_counts(engine) == (len(items), 0)
     monkeypatch.setenv("ABPOA_HIP_NODIR", "1")
-    _launch(items, False, f"small windows, records {golden}")
-    assert _dir_counts(engine) == (0, 0)
-    _launch(items, True, f"small windows, trace {golden}")
+    launch(items, False, f"small windows, records {golden}")
+    assert dir_counts(engine) == (0, 0)
+    launch(items, True, f"small windows, trace {golden}")
 
 
 @pytest.mark.parametrize("golden", NP.GOLDENS)
@@ -188,10 +151,10 @@ def test_one_launch_mixing_every_family(engine, golden):
     order = fams[:3] + [None] + fams[3:]
     for names in (order, order[::-1]):
         items = [(str(f), *_case(golden, f, "own", None)) for f in names]
-        _launch(items, True, f"mixed launch {golden}")
-        _dir_counts(engine)
-        _launch(items, False, f"mixed launch {golden}")
-        assert _dir_counts(engine) == (len(items) - 2, 0)
+        launch(items, True, f"mixed launch {golden}")
+        dir_counts(engine)
+        launch(items, False, f"mixed launch {golden}")
+        assert dir_counts(engine) == (len(items) - 2, 0)
 
 
 @pytest.mark.parametrize("key", [k for k in GROUPS if k[1] in NP.ZDROP], ids=[i for i, k in zip(GROUP_IDS, GROUPS) if k[1] in NP.ZDROP])
@@ -201,11 +164,11 @@ def test_extension_mode_with_zdrop(engine, key):
     items = _group(key)
     stopped = [f for f, c, _, o in items if (o.dp_beg_sn[1:c.n_rows - 1] < 0).any()]
     assert stopped == [f for f in GROUPS[key] if (key[0], f, key[1]) in NP.STOPS_EARLY]
-    outs = _launch(items, True, f"extension z-drop {key}")
+    outs = launch(items, True, f"extension z-drop {key}")
     for (f, c, _, o), h in zip(items, outs):
         assert (h.best_score, h.best_row, h.best_col) == (o.best_score, o.best_row, o.best_col)
         assert np.array_equal(h.dp_beg_sn < 0, o.dp_beg_sn < 0), (key, f)
-    _launch(items, False, f"extension z-drop {key}")
+    launch(items, False, f"extension z-drop {key}")
 
 
 @pytest.mark.parametrize("pt", NP.SWITCH, ids=[NP.point_id(p) for p in NP.SWITCH])
@@ -217,11 +180,11 @@ def test_width_switch(engine, monkeypatch, pt):
     c, d, o = _case(g, f, v, wb)
     bits = NP.VARIANTS[v][1]
     past = wb == NP.W_128[bits] + 1
-    assert _plan(c, bits) == ((NP.RING_ROWS_192[(g, bits)], 192) if past else (16, 128))
-    _launch([(f, c, d, o)], True, f"width switch {pt}")
-    _dir_counts(engine)
-    _launch([(f, c, d, o)], False, f"width switch {pt}")
-    assert _dir_counts(engine) == (1, 0)
+    assert narrow_plan(c, bits) == ((NP.RING_ROWS_192[(g, bits)], 192) if past else (16, 128))
+    launch([(f, c, d, o)], True, f"width switch {pt}")
+    dir_counts(engine)
+    launch([(f, c, d, o)], False, f"width switch {pt}")
+    assert dir_counts(engine) == (1, 0)
 
 
 # ---------------------------------------------------------------- real graphs through both forms of the device-resident driver
@@ -244,60 +207,27 @@ def high_in_degree(msa_rows):
     return sum(1 for s in preds.values() if 5 <= len(s) <= 8), sum(1 for s in preds.values() if len(s) >= 9)
 
 
-_WORKER = r"""
-import ctypes, json, os, sys
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, 'tests'))
-import numpy as np
-import helpers as H, narrow_preds as T
-from abpoa_amd import api, ffi, seqio
-def digests(lib, sets, m):
-    lib.abpoa_hip__cigar_digest.restype = ctypes.c_ulonglong
-    out = []
-    for s in sets:
-        a = np.ascontiguousarray(seqio.encode(s[0], m), np.uint8)
-        out.append(int(lib.abpoa_hip__cigar_digest(a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(a), 0)))
-    lib.abpoa_hip__cigar_digest(None, 0, 1)
-    return out
-def record(res, dig, n_reads):
-    return dict(status=[r.status for r in res], cons=[r.cons_seq for r in res], cov=[list(map(int, r.cons_cov)) for r in res], n_cells=[int(r.n_cells) for r in res],
-                msa=[list(r.msa_seq) for r in res], dig=dig)
-lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0)); shim = H.cpu_shim_lib()
-p = api.Params(**T.AFFINE)
-report = {}
-for kind in T.KINDS:
-    sets = T.read_sets(kind); n_reads = T.KINDS[kind]['n_reads']
-    rep = {}
-    ref = api.msa_batch(sets, p, out_msa=True, n_threads=4, lib=shim)
-    rep['shim'] = record(ref, digests(shim, sets, p.m), n_reads)
-    forms = dict(T.FORMS); forms.update({f: e for (k, f), e in T.EXTRA.items() if k == kind})
-    for form, env in forms.items():
-        run = sets[:1] if (kind, form) in T.EXTRA else sets
-        for k, v in env.items(): os.environ[k] = v
-        res = api.msa_batch(run, p, out_msa=True, n_threads=4)
-        rep[form] = record(res, digests(lib, run, p.m), n_reads)
-        rep[form]['n_host_sets'] = int(api.msa_timing()['n_host_sets']); rep[form]['host_reasons'] = api.host_reasons()
-        for k in env: del os.environ[k]
-    report[kind] = rep
-print('REPORT ' + json.dumps(report))
-"""
+def make_jobs():
+    """{kind: spec} for tests/readset_worker.py: every kind of read-set in every form of the driver, `devsync` on the first set of err30 only."""
+    jobs = {}
+    for kind in KINDS:
+        extra = {f: e for (k, f), e in EXTRA.items() if k == kind}
+        jobs[kind] = dict(params=AFFINE, sets=NP.read_sets(kind), forms=dict(FORMS, **extra), first_set_forms=tuple(extra), ref_first=True,
+                          record=("n_cells", "msa", "dig", "n_host_sets", "host_reasons"), ref_record=("n_cells", "msa", "dig"))
+    return jobs
 
 
 @pytest.fixture(scope="module")
 def report():
-    env = dict(os.environ, ABPOA_HIP_CIGAR_DIGEST="1")
-    for k in ("ABPOA_HIP_DBG", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_DEVSYNC", "ABPOA_HIP_NODIR", "ABPOA_HIP_VERBOSE"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", _WORKER % dict(root=ROOT)], capture_output=True, text=True, env=env, timeout=300)
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("REPORT ")]
-    assert r.returncode == 0 and lines, (r.stdout[-1500:], r.stderr[-3000:])
-    return json.loads(lines[0][7:])
+    return run_report("test_gpu_narrow_bodies", set_env={"ABPOA_HIP_CIGAR_DIGEST": "1"}, timeout=300,
+                      clear_env=("ABPOA_HIP_DBG", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_DEVSYNC", "ABPOA_HIP_NODIR", "ABPOA_HIP_VERBOSE"))
 
 
 @pytest.mark.parametrize("kind", ["err30", "ins16"])
 def test_read_sets_grow_high_in_degree(report, kind):
     """On the shim's output (CPU side): the final graph of every set, rebuilt from its MSA rows, has 100 and more nodes of 5-8 distinct predecessors
     (measured 148-169 at 30 % error, 143-153 at the insertion-heavy rates; the 1 kb benchmark sets at 5 % have about 55), some of 9 and more."""
-    ref = report[kind]["shim"]
+    ref = report[kind]["ref"]
     n_reads = KINDS[kind]["n_reads"]
     counts = [high_in_degree(rows[:n_reads]) for rows in ref["msa"]]
     print(kind, counts)
@@ -312,9 +242,9 @@ def test_device_driver_on_divergent_read_sets(report, kind):
     and n_cells equal the shim's, the cigar digests are equal across the forms (and to the shim's), no set leaves the device.  The 50-read sets climb the
     node-slot ladder (graphs of five read lengths), the 20-read set stays in the first pass; one set once more under ABPOA_HIP_DEVSYNC=1."""
     rep = report[kind]
-    ref = rep["shim"]
+    ref = rep["ref"]
     assert all(s == 0 for s in ref["status"]) and all(d != 0 for d in ref["dig"])
-    forms = [f for f in rep if f != "shim"]
+    forms = [f for f in rep if f != "ref"]
     assert set(FORMS) <= set(forms) and (("devsync" in forms) == (kind == "err30"))
     for form in forms:
         got = rep[form]

@@ -3,18 +3,15 @@ schedule, the results are the same: for every job below the cigar digests (ABPOA
 device), the consensus records and the per-set status are identical in three forms -- the default, the late start (ABPOA_HIP_LATE_TAIL=1) and one wavefront
 per backtrack (ABPOA_HIP_DBG bit 10) -- and equal to the CPU build of the host layer whose aligner is the plain-C oracle (tests/cpu_shim.cpp).
 
-The digest switch is read once per process, so ONE child process runs every job in every form and reports; the tests below look at its report.  Nothing
-here depends on timing: a helper that starts early, late or not at all leaves the same cigar."""
-import json
-import os
+The digest switch is read once per process, so ONE child process (tests/readset_worker.py) runs every job of make_jobs() in every form and reports; the tests
+below look at its report.  Nothing here depends on timing: a helper that starts early, late or not at all leaves the same cigar."""
 import re
-import subprocess
-import sys
 
 import pytest
 
+from readset_worker import run_report
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 AFFINE = dict(gap_open1=4, gap_open2=0, gap_ext1=2)
 FORMS = {"default": {}, "late_start": {"ABPOA_HIP_LATE_TAIL": "1"}, "one_wavefront": {"ABPOA_HIP_DBG": "1024"}}
@@ -35,70 +32,32 @@ JOBS = {
     "linear": (dict(gap_open1=0, gap_open2=0, gap_ext1=2), [(6, 800 + 23 * i) for i in range(4)], None, {}),
 }
 
-WORKER = r"""
-import ctypes, json, os, sys
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, 'tests'))
-import numpy as np
-import helpers as H
-from abpoa_amd import api, ffi, synth, seqio
-JOBS, FORMS = %(jobs)r, %(forms)r
-def digests(lib, sets, m):
-    lib.abpoa_hip__cigar_digest.restype = ctypes.c_ulonglong
-    out = []
-    for s in sets:
-        a = np.ascontiguousarray(seqio.encode(s[0], m), np.uint8)
-        out.append(int(lib.abpoa_hip__cigar_digest(a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(a), 0)))
-    lib.abpoa_hip__cigar_digest(None, 0, 1)
-    return out
-def record(res, dig):
-    return dict(status=[r.status for r in res], cons=[r.cons_seq for r in res], cov=[list(map(int, r.cons_cov)) for r in res], dig=dig)
-lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0)); shim = H.cpu_shim_lib()
-report = {}
-for job, (kw, shapes, stranger, env) in JOBS.items():
-    sets = [synth.make_read_set(61, i, n, ln, 0.05) for i, (n, ln) in enumerate(shapes)]
-    if stranger is not None:
-        for i, (n, ln) in enumerate(shapes): sets[i][stranger] = synth.make_read_set(977, i, 1, ln, 0.0)[0]
-    p = api.Params(**kw)
-    rep = {}
-    for form, fenv in FORMS.items():
-        for k, v in dict(env, **fenv).items(): os.environ[k] = v
-        lib.abpoa_hip_reset_stats()
-        sys.stderr.write('[job] %%s %%s\n' %% (job, form)); sys.stderr.flush()
-        res = api.msa_batch(sets, p, n_threads=4)
-        rep[form] = record(res, digests(lib, sets, p.m))
-        rep[form]['rounds_launches'] = int(ffi.stats()['rounds_launches']); rep[form]['n_host_sets'] = int(api.msa_timing()['n_host_sets'])
-        for k in dict(env, **fenv): del os.environ[k]
-    ref = api.msa_batch(sets, p, n_threads=4, lib=shim)
-    rep['oracle'] = record(ref, digests(shim, sets, p.m))
-    report[job] = rep
-print('REPORT ' + json.dumps(report))
-"""
+
+def make_jobs():
+    """{job: spec} for tests/readset_worker.py."""
+    from abpoa_amd import synth
+    jobs = {}
+    for job, (kw, shapes, stranger, env) in JOBS.items():
+        sets = [synth.make_read_set(61, i, n, ln, 0.05) for i, (n, ln) in enumerate(shapes)]
+        if stranger is not None:
+            for i, (n, ln) in enumerate(shapes):
+                sets[i][stranger] = synth.make_read_set(977, i, 1, ln, 0.0)[0]
+        jobs[job] = dict(params=kw, sets=sets, forms=FORMS, env=env, record=("dig", "rounds_launches", "n_host_sets"), ref_record=("dig",))
+    return jobs
 
 
 @pytest.fixture(scope="module")
 def report():
-    code = WORKER % dict(root=ROOT, jobs=JOBS, forms=FORMS)
-    env = dict(os.environ, ABPOA_HIP_CIGAR_DIGEST="1", ABPOA_HIP_VERBOSE="1")
-    for k in ("ABPOA_HIP_LATE_TAIL", "ABPOA_HIP_DBG", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_ARENA_PCT"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=600)
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("REPORT ")]
-    assert r.returncode == 0 and lines, (r.stdout[-1500:], r.stderr[-3000:])
-    log = {}      # (job, form) -> what the library said on stderr during that run
-    key = None
-    for ln in r.stderr.splitlines():
-        if ln.startswith("[job] "):
-            key = tuple(ln.split()[1:3]); log[key] = []
-        elif key:
-            log[key].append(ln)
-    return json.loads(lines[0][7:]), {k: "\n".join(v) for k, v in log.items()}
+    """(the report, {(job, form): what the library said on stderr during that run})"""
+    return run_report("test_gpu_overlap_tail", set_env={"ABPOA_HIP_CIGAR_DIGEST": "1", "ABPOA_HIP_VERBOSE": "1"}, timeout=600, want_log=True,
+                      clear_env=("ABPOA_HIP_LATE_TAIL", "ABPOA_HIP_DBG", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_ARENA_PCT"))
 
 
 @pytest.mark.parametrize("job", list(JOBS))
 def test_three_schedules_one_result(report, job):
     rep, log = report
     r = rep[job]
-    ref = r["oracle"]
+    ref = r["ref"]
     assert all(s == 0 for s in ref["status"]) and all(d != 0 for d in ref["dig"])
     for form in FORMS:
         got = r[form]

@@ -6,18 +6,10 @@ import numpy as np
 import pytest
 
 import helpers as H
+from gpu_harness import dir_counts, engine  # noqa: F401  (engine: the fixture)
 
 pytestmark = pytest.mark.gpu
 CASES = H.golden_cases()
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1, "no HIP device: the engine has no fallback"
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
 
 
 @pytest.mark.parametrize("label,path", CASES, ids=[c[0] for c in CASES])
@@ -30,11 +22,11 @@ def test_hip_matches_golden_and_oracle(engine, label, path):
     H.compare_outs(h, o, label="hip-vs-oracle " + label)
     # without the trace the fast row loops write direction words instead of score records (dir_plane.h) and the backtrack walks those: best cell, cigar,
     # every abpoa_res_t field and the band state must not change
-    _dir_counts(engine)
+    dir_counts(engine)
     h2 = H.run_hip([case], want_trace=False)[0]
     H.compare_with_golden(h2, g, check_planes=False, label="hip-dir-vs-golden " + label)
     assert np.array_equal(h2.cigar, o.cigar) and h2.best_score == o.best_score
-    walked, redone = _dir_counts(engine)
+    walked, redone = dir_counts(engine)
     if label.startswith(("s1k_", "seq_ag_gb", "heter_ag_gb", "heter_cg_gb")):      # global, narrow band, default penalties: the plane must have been used
         assert walked == 1 and redone == 0, (label, walked, redone)
 
@@ -149,7 +141,7 @@ def test_need_scores_redo_path(engine, monkeypatch):
     the words, so that the redo path runs: same results, and the counters say that alignments were redone."""
     monkeypatch.setenv("ABPOA_HIP_DBG", "512")
     engine.abpoa_hip_reset_stats()
-    _dir_counts(engine)
+    dir_counts(engine)
     n = redone_total = 0
     for label, path in CASES:
         if not label.startswith(("s1k_", "heter_ag_gb", "heter_cg_gb")):
@@ -157,7 +149,7 @@ def test_need_scores_redo_path(engine, monkeypatch):
         g = H.read_abpg(path)
         h = H.run_hip([H.FlatCase(g)], want_trace=False)[0]
         H.compare_with_golden(h, g, check_planes=False, label=f"need-scores {label}")
-        walked, redone = _dir_counts(engine)
+        walked, redone = dir_counts(engine)
         redone_total += redone
         n += 1
     assert n >= 3 and redone_total >= 1, (n, redone_total)
@@ -170,13 +162,6 @@ def test_need_scores_redo_path(engine, monkeypatch):
     ref = api.msa_batch(sets, p, n_threads=4)
     for a, b_ in zip(dev, ref):
         assert a.status == 0 and b_.status == 0 and a.cons_seq == b_.cons_seq and a.cons_cov == b_.cons_cov
-
-
-def _dir_counts(lib):
-    import ctypes
-    out = (ctypes.c_longlong * 2)()
-    lib.abpoa_hip__dir_counts(out)
-    return out[0], out[1]
 
 
 def test_hip_batch_mixed_widths(engine):

@@ -5,19 +5,16 @@ order, row_pd, row_sdist and, for general-kernel jobs, out_off / out_row.
 A wrong remaining length only moves a band, a wrong row_sdist only changes which rows keep their records, and the order of a predecessor list only breaks ties:
 none has to change a consensus, so the tables themselves are checked.  Under ABPOA_HIP_DEVSYNC=1 the library downloads them after every prepare launch and
 compares them with a plain serial recomputation from the host graph (DeviceDebug::prepare_check; the first four sets of a job, so no job here has more).  The same jobs also run in the default form (the all-rounds kernel where it applies) and with ABPOA_HIP_LOCKSTEP=1 against the
-CPU build of the host layer whose aligner is the plain-C oracle: status, cigar digests (every graph cigar of a set folded into 64 bits), consensus, coverage.  ONE child process runs everything and reports."""
-import json
-import os
+CPU build of the host layer whose aligner is the plain-C oracle: status, cigar digests (every graph cigar of a set folded into 64 bits), consensus, coverage.  ONE child process
+(tests/readset_worker.py) runs every job of make_jobs() in every form and reports."""
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from readset_worker import run_report
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 AFFINE = dict(gap_open1=4, gap_open2=0, gap_ext1=2)
 
@@ -67,9 +64,13 @@ def degrees_from_msa(msa, n_reads):
     return max(len(v) for v in ins.values()), max(len(v) for v in outs.values())
 
 
+FORMS = {"default": {}, "lockstep": {"ABPOA_HIP_LOCKSTEP": "1"}, "devsync": {"ABPOA_HIP_DEVSYNC": "1", "ABPOA_HIP_HOSTGRAPH": "0"}}
+
+
 def make_jobs():
+    """{job: spec} for tests/readset_worker.py."""
     from abpoa_amd import synth
-    return {
+    table = {
         # rows = first read + 2, then more: the 64-row edge of a lane's records, the 256-row edge of a thread's next row, the 1 024- and 2 048-row edges that
         # four and eight rows of a thread lie across
         "tiny": (AFFINE, [synth.make_read_set(31, i, 4, ln, 0.0) for i, ln in enumerate((1, 2, 3))]),
@@ -91,63 +92,14 @@ def make_jobs():
         # linear gaps with the band: no direction words, so the DP does not read row_sdist
         "linear": (dict(gap_open1=0, gap_open2=0, gap_ext1=2), [synth.make_read_set(48, i, 6, 300, 0.05) for i in range(2)]),
     }
-
-
-WORKER = r"""
-import ctypes, json, os, sys
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, 'tests'))
-import numpy as np
-import helpers as H
-from abpoa_amd import api, ffi, seqio
-import test_gpu_prepare_tables as T
-def digests(lib, sets, m):      # ABPOA_HIP_CIGAR_DIGEST: every graph cigar of a set folded into 64 bits, looked up by the set's first read
-    lib.abpoa_hip__cigar_digest.restype = ctypes.c_ulonglong
-    out = []
-    for s in sets:
-        a = np.ascontiguousarray(seqio.encode(s[0], m), np.uint8)
-        out.append(int(lib.abpoa_hip__cigar_digest(a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(a), 0)))
-    lib.abpoa_hip__cigar_digest(None, 0, 1)
-    return out
-FORMS = (('default', {}), ('lockstep', {'ABPOA_HIP_LOCKSTEP': '1'}), ('devsync', {'ABPOA_HIP_DEVSYNC': '1', 'ABPOA_HIP_HOSTGRAPH': '0'}))
-def record(res):
-    return dict(status=[r.status for r in res], cons=[r.cons_seq for r in res], cov=[list(map(int, r.cons_cov)) for r in res])
-lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0)); shim = H.cpu_shim_lib()
-report = {}
-for job, (kw, sets) in T.make_jobs().items():
-    p = api.Params(**kw)
-    rep = {}
-    for form, env in FORMS:
-        os.environ.update(env)
-        sys.stderr.write('[job] %%s %%s\n' %% (job, form)); sys.stderr.flush()
-        rep[form] = record(api.msa_batch(sets, p, n_threads=4))
-        rep[form]['dig'] = digests(lib, sets, p.m)
-        rep[form]['n_host_sets'] = int(api.msa_timing()['n_host_sets'])
-        for k in env: del os.environ[k]
-    ref = api.msa_batch(sets, p, out_cons=True, out_msa=True, n_threads=4, lib=shim)
-    rep['oracle'] = record(ref)
-    rep['oracle']['dig'] = digests(shim, sets, p.m)
-    rep['oracle']['msa'] = [r.msa_seq for r in ref]
-    rep['n_reads'] = [len(s) for s in sets]
-    report[job] = rep
-print('REPORT ' + json.dumps(report))
-"""
+    return {job: dict(params=kw, sets=sets, forms=FORMS, record=("dig", "n_host_sets"), ref_record=("dig", "msa")) for job, (kw, sets) in table.items()}
 
 
 @pytest.fixture(scope="module")
 def report():
-    env = dict(os.environ, ABPOA_HIP_CIGAR_DIGEST="1")
-    for k in ("ABPOA_HIP_DEVSYNC", "ABPOA_HIP_HOSTGRAPH", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_DBG"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", WORKER % dict(root=ROOT)], capture_output=True, text=True, env=env, timeout=600)
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("REPORT ")]
-    assert r.returncode == 0 and lines, (r.stdout[-1500:], r.stderr[-3000:])
-    log, key = {}, None
-    for ln in r.stderr.splitlines():
-        if ln.startswith("[job] "):
-            key = tuple(ln.split()[1:3]); log[key] = []
-        elif key:
-            log[key].append(ln)
-    return json.loads(lines[0][7:]), {k: "\n".join(v) for k, v in log.items()}
+    """(the report, {(job, form): what the library said on stderr during that run})"""
+    return run_report("test_gpu_prepare_tables", set_env={"ABPOA_HIP_CIGAR_DIGEST": "1"}, timeout=600, want_log=True,
+                      clear_env=("ABPOA_HIP_DEVSYNC", "ABPOA_HIP_HOSTGRAPH", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_DBG"))
 
 
 JOBS = ["tiny", "edge_64", "edge_256", "edge_1024", "edge_2048", "convex_2048", "long_2700", "degrees", "ragged_20", "local", "general", "linear"]
@@ -164,7 +116,7 @@ def test_tables_equal_the_host_recomputation(report, job):
     text = log[(job, "devsync")]
     assert "FAILED" not in text, "\n".join(ln for ln in text.splitlines() if "FAILED" in ln or "remaining length" in ln)[:3000]
     checks = re.findall(r"set (\d+) round (\d+): prepare check ok \((\d+) rows, 0 differences\)", text)
-    assert len(checks) == sum(n - 1 for n in rep[job]["n_reads"]), text[-2000:]
+    assert len(checks) == sum(len(s) - 1 for s in make_jobs()[job]["sets"]), text[-2000:]
 
 
 def test_the_graphs_cross_the_edges_aimed_at(report):
@@ -183,9 +135,9 @@ def test_the_jobs_take_the_paths_they_are_about(report):
     rep, log = report
     for job in JOBS:
         assert ("successor rows too" in log[(job, "devsync")]) == (job == "general"), job
-    for msa, reads, d in zip(rep["degrees"]["oracle"]["msa"], make_jobs()["degrees"][1], DEGREES):
+    for msa, reads, d in zip(rep["degrees"]["ref"]["msa"], make_jobs()["degrees"]["sets"], DEGREES):
         assert degrees_from_msa(msa, len(reads)) == (d, d)
-    msa = rep["ragged_20"]["oracle"]["msa"][0]
+    msa = rep["ragged_20"]["ref"]["msa"][0]
     starts = {next(i for i, c in enumerate(row) if c != "-") for row in msa[:20]}
     ends = {max(i for i, c in enumerate(row) if c != "-") for row in msa[:20]}
     assert len(starts) == 20 and len(ends) == 20
@@ -195,9 +147,9 @@ def test_the_jobs_take_the_paths_they_are_about(report):
 def test_results_equal_the_oracle_backed_run(report, job):
     rep, log = report
     r = rep[job]
-    ref = r["oracle"]
+    ref = r["ref"]
     assert all(s == 0 for s in ref["status"])
-    for form in ("default", "lockstep", "devsync"):
+    for form in FORMS:
         got = r[form]
         assert got["n_host_sets"] == 0, f"{job} / {form}: sets on the host driver"
         assert (got["status"], got["cons"], got["cov"]) == (ref["status"], ref["cons"], ref["cov"]), f"{job} / {form}: differs from the oracle-backed run"

@@ -5,15 +5,14 @@ API, without the trace (direction words or score records, the backtrack), and wh
 host layer.  tests/test_oracle_vs_reference.py::test_scoring_points pins the oracle to the compiled reference at the same points, and
 tests/test_scoring_regimes.py that the re-scored goldens enter the regimes named here."""
 import ctypes
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import helpers as H
 import scoring_points as SP
+from gpu_harness import dir_counts, engine, launch  # noqa: F401  (engine: the fixture)
+from readset_worker import run_report
 
 pytestmark = pytest.mark.gpu
 NARROW = ["s1k_ag_gb", "s1k_cg_gb", "seq_ag_gb", "heter_cg_gb"]      # global, band of the default width: the direction plane where the penalties allow it
@@ -21,15 +20,6 @@ GB = NARROW + ["ragged_ag_gb"]
 EXT = ["seq_cg_ext", "seq_ag_extz"]
 LOC = ["seq_cg_loc", "ragged_ag_loc"]
 COMP = str.maketrans("ACGTN", "TGCAN")
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1, "no HIP device: the engine has no fallback"
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
 
 
 _GOLD, _CASES = {}, {}
@@ -47,21 +37,12 @@ def _case(name, pt, wb=None, wf=None):
     return _CASES[k]
 
 
-def _dir_counts(lib):
-    out = (ctypes.c_longlong * 2)()
-    lib.abpoa_hip__dir_counts(out)
-    return out[0], out[1]
-
-
 def _both_ways(names, pt, wb=None, wf=None, label=""):
     """One launch per group of alignments that share every Scoring field: with the trace (bands, every plane cell, row arg-max) and without it (cigar, best
     cell, result fields, band state) against the oracle."""
-    items = [_case(n, pt, wb, wf) for n in names]
+    items = [(n, *_case(n, pt, wb, wf)) for n in names]
     for trace in (True, False):
-        outs = H.run_hip([c for c, _, _ in items], want_trace=trace)
-        for n, h, (_, _, o) in zip(names, outs, items):
-            assert hasattr(h, "dp_beg") == trace
-            H.compare_outs(h, o, label=f"{label}{pt.name} {n} wb={wb} trace={trace}")
+        launch(items, trace, f"{label}{pt.name} wb={wb}")
 
 
 @pytest.mark.parametrize("pt", SP.POINTS, ids=[p.name for p in SP.POINTS])
@@ -75,11 +56,9 @@ def test_every_point_at_plane_level_and_through_the_backtrack(engine, monkeypatc
         monkeypatch.setenv("ABPOA_HIP_LOCAL_TEAM", team)
         _both_ways(LOC, pt, label=f"local team={team} ")
     monkeypatch.delenv("ABPOA_HIP_LOCAL_TEAM")
-    _dir_counts(engine)
-    items = [_case(n, pt) for n in NARROW]
-    for h, (_, _, o), n in zip(H.run_hip([c for c, _, _ in items], want_trace=False), items, NARROW):
-        H.compare_outs(h, o, label=f"{pt.name} {n} narrow")
-    walked, redone = _dir_counts(engine)
+    dir_counts(engine)
+    launch([(n, *_case(n, pt)) for n in NARROW], False, f"{pt.name} narrow")
+    walked, redone = dir_counts(engine)
     print(f"{pt.name}: direction plane usable {pt.dir_usable()}, walked {walked} of {len(NARROW)}, redone with records {redone}")
     assert walked == (len(NARROW) if pt.dir_usable() else 0), (pt.name, walked, redone)
 
@@ -172,9 +151,7 @@ def test_both_sides_of_the_score_width_gate(engine, name):
         c, _, o = _case(name, pt)
         assert lib.abpoa_oracle_score_bits(ctypes.byref(c.sc), c.n_rows, c.qlen, None) == bits and o.bits == bits
         for trace in (True, False):
-            h = H.run_hip([c], want_trace=trace)[0]
-            assert h.bits == bits, (pt.name, name, h.bits)
-            H.compare_outs(h, o, label=f"{pt.name} {name} trace={trace}")
+            launch([(name, c, o)], trace, pt.name, bits=bits)
         print(f"{pt.name} {name}: {bits} bits, best score {o.best_score}")
 
 
@@ -251,40 +228,22 @@ def test_assembly_row_loop_equals_the_compilers_under_an_asymmetric_matrix(engin
     _device_equals_host(ASYM_AG_O7, label="compiler ")
 
 
-_DIGEST_WORKER = r"""
-import ctypes, sys
-sys.path.insert(0, %(root)r); sys.path.insert(0, %(root)r + '/tests')
-import numpy as np
-import helpers as H, scoring_points as SP, test_gpu_scoring as T
-from abpoa_amd import api, ffi, seqio
-def digests(lib, sets, m):
-    lib.abpoa_hip__cigar_digest.restype = ctypes.c_ulonglong
-    out = []
-    for s in sets:
-        a = np.ascontiguousarray(seqio.encode(s[0], m), np.uint8)
-        out.append(int(lib.abpoa_hip__cigar_digest(a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(a), 0)))
-    lib.abpoa_hip__cigar_digest(None, 0, 1)
-    return out
-lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0)); shim = H.cpu_shim_lib()
-sets = T._sets()
-for name in %(names)r:
-    p = SP.BY_NAME[name].params()
-    dev = api.msa_batch(sets, p, n_threads=4); nh = api.msa_timing()['n_host_sets']
-    if nh: print(name, nh, 'set(s) left the device:', api.host_reasons())
-    d_dev = digests(lib, sets, p.m)
-    host = api.msa_batch(sets, p, n_threads=8, lib=shim)
-    d_host = digests(shim, sets, p.m)
-    assert all(r.status == 0 for r in dev) and all(d != 0 for d in d_dev) and d_dev == d_host, (name, d_dev, d_host)
-    assert [r.cons_seq for r in dev] == [r.cons_seq for r in host], name
-    print('CIGARS EQUAL', name)
-"""
+DIGEST_POINTS = ["asym_cg", "hox_cg"]
+
+
+def make_jobs():
+    """{point: spec} for tests/readset_worker.py: the six sets under one ASYM5 and one HOXD70 point, on the device and through the oracle-backed host layer."""
+    return {name: dict(params=SP.BY_NAME[name].params(), sets=_sets(), forms={"device": {}}, record=("dig", "n_host_sets", "host_reasons"),
+                       ref_record=("dig",), ref_threads=8) for name in DIGEST_POINTS}
 
 
 def test_device_driver_cigars_under_the_matrices(engine):
     """Every graph cigar of the six sets, folded into a digest per set on the device (ABPOA_HIP_CIGAR_DIGEST=1, read once per process: a child process)
     and by the oracle-backed host layer: one ASYM5 and one HOXD70 job."""
-    names = ["asym_cg", "hox_cg"]
-    r = subprocess.run([sys.executable, "-c", _DIGEST_WORKER % dict(root=H.ROOT, names=names)], capture_output=True, text=True,
-                       env=dict(os.environ, ABPOA_HIP_CIGAR_DIGEST="1"), timeout=300)
-    print(r.stdout[-2000:])
-    assert r.returncode == 0 and all(f"CIGARS EQUAL {n}" in r.stdout for n in names), (r.stdout[-1500:], r.stderr[-3000:])
+    rep = run_report("test_gpu_scoring", set_env={"ABPOA_HIP_CIGAR_DIGEST": "1"}, clear_env=(), timeout=300)
+    for name in DIGEST_POINTS:
+        dev, ref = rep[name]["device"], rep[name]["ref"]
+        if dev["n_host_sets"]:
+            print(name, dev["n_host_sets"], "set(s) left the device:", dev["host_reasons"])
+        assert all(s == 0 for s in dev["status"]) and all(d != 0 for d in dev["dig"]) and dev["dig"] == ref["dig"], (name, dev["dig"], ref["dig"])
+        assert dev["cons"] == ref["cons"], name

@@ -14,16 +14,12 @@ Read lengths (sets of 6 reads at 5 % error; a set's five graphs grow by about 3 
                 more than one block of the final pass.
 "no_splice": one read of the set has nothing to do with the graph (the main walk meets no helper: one segment, and helpers that come to the pass late);
 "capacity": arenas that run out in mid-graph (the row loop ends with a status: the main wavefront's "no pass" word).
-One child process runs every job in every form.  Nothing here depends on timing, and nothing provokes a fault or a hang."""
-import json
-import os
-import subprocess
-import sys
-
+One child process (tests/readset_worker.py) runs every job of make_jobs() in every form.  Nothing here depends on timing, and nothing provokes a fault or a hang."""
 import pytest
 
+from readset_worker import run_report
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 AFFINE = dict(gap_open1=4, gap_open2=0, gap_ext1=2)
 FORMS = {"default": {}, "late_start": {"ABPOA_HIP_LATE_TAIL": "1"}, "one_wavefront": {"ABPOA_HIP_DBG": "1024"}}
@@ -37,66 +33,30 @@ JOBS = {
     "capacity": ([(6, 800 + 17 * i) for i in range(4)], None, {"ABPOA_HIP_ARENA_PCT": "6", "ABPOA_HIP_NO_PASS_HINT": "1"}),
 }
 
-WORKER = r"""
-import ctypes, json, os, sys
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, 'tests'))
-import numpy as np
-import helpers as H
-from abpoa_amd import api, ffi, synth, seqio
-JOBS, FORMS = %(jobs)r, %(forms)r
-def per_set(lib, sets, m, last):
-    lib.abpoa_hip__cigar_digest.restype = ctypes.c_ulonglong
-    dig, rec = [], []
-    for s in sets:
-        a = np.ascontiguousarray(seqio.encode(s[0], m), np.uint8)
-        pa = a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))
-        dig.append(int(lib.abpoa_hip__cigar_digest(pa, len(a), 0)))
-        if last:
-            v = (ctypes.c_int * 8)()
-            rec.append(list(v) if lib.abpoa_hip__last_aln(pa, len(a), v, 0) else None)
-    lib.abpoa_hip__cigar_digest(None, 0, 1)
-    if last: lib.abpoa_hip__last_aln(None, 0, None, 1)
-    return dig, rec
-def record(res, dig, rec):
-    return dict(status=[r.status for r in res], cons=[r.cons_seq for r in res], cov=[list(map(int, r.cons_cov)) for r in res], dig=dig, last=rec)
-lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0)); shim = H.cpu_shim_lib()
-report = {}
-for job, (shapes, stranger, env) in JOBS.items():
-    sets = [synth.make_read_set(73, i, n, ln, 0.05) for i, (n, ln) in enumerate(shapes)]
-    if stranger is not None:
-        for i, (n, ln) in enumerate(shapes): sets[i][stranger] = synth.make_read_set(977, i, 1, ln, 0.0)[0]
-    p = api.Params(**%(affine)r)
-    rep = {}
-    for form, fenv in FORMS.items():
-        for k, v in dict(env, **fenv).items(): os.environ[k] = v
-        lib.abpoa_hip_reset_stats()
-        res = api.msa_batch(sets, p, n_threads=4)
-        rep[form] = record(res, *per_set(lib, sets, p.m, True))
-        rep[form]['rounds_launches'] = int(ffi.stats()['rounds_launches']); rep[form]['n_host_sets'] = int(api.msa_timing()['n_host_sets'])
-        for k in dict(env, **fenv): del os.environ[k]
-    ref = api.msa_batch(sets, p, n_threads=4, lib=shim)
-    rep['oracle'] = record(ref, *per_set(shim, sets, p.m, False))
-    report[job] = rep
-print('REPORT ' + json.dumps(report))
-"""
+
+def make_jobs():
+    """{job: spec} for tests/readset_worker.py."""
+    from abpoa_amd import synth
+    jobs = {}
+    for job, (shapes, stranger, env) in JOBS.items():
+        sets = [synth.make_read_set(73, i, n, ln, 0.05) for i, (n, ln) in enumerate(shapes)]
+        if stranger is not None:
+            for i, (n, ln) in enumerate(shapes):
+                sets[i][stranger] = synth.make_read_set(977, i, 1, ln, 0.0)[0]
+        jobs[job] = dict(params=AFFINE, sets=sets, forms=FORMS, env=env, record=("dig", "last", "rounds_launches", "n_host_sets"), ref_record=("dig",))
+    return jobs
 
 
 @pytest.fixture(scope="module")
 def report():
-    code = WORKER % dict(root=ROOT, jobs=JOBS, forms=FORMS, affine=AFFINE)
-    env = dict(os.environ, ABPOA_HIP_CIGAR_DIGEST="1")
-    for k in ("ABPOA_HIP_LATE_TAIL", "ABPOA_HIP_DBG", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_ARENA_PCT", "ABPOA_HIP_VERBOSE"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=600)
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("REPORT ")]
-    assert r.returncode == 0 and lines, (r.stdout[-1500:], r.stderr[-3000:])
-    return json.loads(lines[0][7:])
+    return run_report("test_gpu_tail_final_pass", set_env={"ABPOA_HIP_CIGAR_DIGEST": "1"}, timeout=600,
+                      clear_env=("ABPOA_HIP_LATE_TAIL", "ABPOA_HIP_DBG", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_ARENA_PCT", "ABPOA_HIP_VERBOSE"))
 
 
 @pytest.mark.parametrize("job", list(JOBS))
 def test_three_forms_and_the_oracle(report, job):
     r = report[job]
-    ref = r["oracle"]
+    ref = r["ref"]
     assert all(s == 0 for s in ref["status"]) and all(d != 0 for d in ref["dig"])
     for form in FORMS:
         got = r[form]

@@ -6,26 +6,16 @@ to 11 per golden and width, both ends of the wide loop's range (wide_w_lo = 40, 
 past each, the bodies' "wider than my chunks" decline at 8 / 12 chunks, the plan turning the fast loops off).  tests/test_wide_band_regimes.py asserts those
 properties of the inputs and the plan on the CPU, tests/test_oracle_vs_reference.py pins the oracle to the compiled reference at three of the bands, and the
 diagnostic build's row counters (tests/test_gpu_device_msa.py::test_long_read_rows_take_the_all_chunk_bodies) show on the device that the rows took the bodies."""
-import ctypes
-
 import numpy as np
 import pytest
 
 import helpers as H
 import wide_bands as WB
+from gpu_harness import dir_counts, engine, launch  # noqa: F401  (engine: the fixture)
 from test_wide_band_regimes import mixed_cases
 
 pytestmark = pytest.mark.gpu
 IDS = [f"{g}_i{b}" for g, b in WB.COMBOS]
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1, "no HIP device: the engine has no fallback"
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
 
 
 _GOLD, _CASES = {}, {"combo": None, "items": {}}
@@ -49,37 +39,15 @@ def _case(golden, bits, wb):
     return items[wb]
 
 
-def _one(case):
-    outs = H.run_hip([case], want_trace=True)
-    assert len(outs) == 1 and outs[0].status == 0
-    return outs[0]
-
-
-def _dir_counts(lib):
-    out = (ctypes.c_longlong * 2)()
-    lib.abpoa_hip__dir_counts(out)
-    return out[0], out[1]
-
-
-def _with_trace(golden, bits, bands, label):
-    """Score records, trace kept: bands, every plane cell, row arg-max, best cell, cigar, result fields, band state."""
+def _with_trace(golden, bits, bands, label, trace=True):
+    """One launch per band.  Score records, trace kept: bands, every plane cell, row arg-max, best cell, cigar, result fields, band state."""
     for wb in bands:
-        c, _, o = _case(golden, bits, wb)
-        h = _one(c)
-        assert hasattr(h, "dp_beg") and h.bits == bits
-        H.compare_outs(h, o, label=f"{label} {golden} int{bits} wb={wb}")
+        launch([(f"wb={wb}", *_case(golden, bits, wb))], trace, f"{label} {golden} int{bits}", bits=bits)
 
 
 def _without_trace(golden, bits, bands, label):
     """No trace: best cell, cigar, result fields, band state."""
-    outs = []
-    for wb in bands:
-        c, _, o = _case(golden, bits, wb)
-        hs = H.run_hip([c], want_trace=False)
-        assert len(hs) == 1 and hs[0].status == 0 and not hasattr(hs[0], "dp_beg") and hs[0].bits == bits
-        H.compare_outs(hs[0], o, label=f"{label} {golden} int{bits} wb={wb}")
-        outs.append(hs[0])
-    return outs
+    _with_trace(golden, bits, bands, label, trace=False)
 
 
 NO_WORDS = WB.NO_WORDS      # (point, words variant) pairs that are not run, each with its reason; tests/test_wide_band_regimes.py holds the table to the plan
@@ -94,9 +62,9 @@ def test_records_with_trace(engine, golden, bits):
 def test_records_without_trace(engine, monkeypatch, golden, bits):
     """ABPOA_HIP_NODIR=1: the record walk (backtrack.h) over the column-slice windows of rows this wide."""
     monkeypatch.setenv("ABPOA_HIP_NODIR", "1")
-    _dir_counts(engine)
+    dir_counts(engine)
     _without_trace(golden, bits, WB.BANDS, "records, no trace")
-    assert _dir_counts(engine) == (0, 0)
+    assert dir_counts(engine) == (0, 0)
 
 
 @pytest.mark.parametrize("golden,bits", WB.COMBOS, ids=IDS)
@@ -105,9 +73,9 @@ def test_direction_words(engine, monkeypatch, golden, bits):
     the plane and none is redone with records (dir_plane_usable holds at both scorings)."""
     monkeypatch.setenv("ABPOA_HIP_DIR_WIDE", "1")
     for wb in WB.BANDS:
-        _dir_counts(engine)
+        dir_counts(engine)
         _without_trace(golden, bits, [wb], "words")
-        walked, redone = _dir_counts(engine)
+        walked, redone = dir_counts(engine)
         assert (walked, redone) == ((0, 0) if (golden, bits, wb) in NO_WORDS else (1, 0)), (golden, bits, wb, walked, redone)
 
 
@@ -154,14 +122,10 @@ def test_mixed_launch(engine, bits32):
     of 3-8 chunks and, at the gate point, up to 15); at match = the int32 gate point of the longest query that query runs in 32 bits beside six in 16.  Every
     alignment against the oracle, planes included, order preserved; then without the trace."""
     cases = mixed_cases(bits32)
-    oracle = [H.run_oracle(c) for _, c in cases]
-    assert {o.bits for o in oracle} == ({16, 32} if bits32 else {16})
+    items = [(label, c, H.run_oracle(c)) for label, c in cases]
+    assert {o.bits for _, _, o in items} == ({16, 32} if bits32 else {16})
     for trace in (True, False):
-        outs = H.run_hip([c for _, c in cases], want_trace=trace)
-        assert len(outs) == len(cases)
-        for (label, _), h, o in zip(cases, outs, oracle):
-            assert h.status == 0 and hasattr(h, "dp_beg") == trace
-            H.compare_outs(h, o, label=f"mixed launch {label} trace={trace}")
+        launch(items, trace, "mixed launch")
 
 
 @pytest.mark.parametrize("wb,at_least", WB.EXTZ_BANDS, ids=[f"wb{w}" for w, _ in WB.EXTZ_BANDS])
@@ -178,8 +142,6 @@ def test_extension_mode_with_zdrop(engine, wb, at_least):
         c = H.FlatCase(d)
         o = H.run_oracle(c)
         for trace in (True, False):
-            hs = H.run_hip([c], want_trace=trace)
-            assert len(hs) == 1 and hs[0].status == 0 and hasattr(hs[0], "dp_beg") == trace
-            H.compare_outs(hs[0], o, label=f"extension z-drop {label} wb={wb} trace={trace}")
+            launch([(label, c, o)], trace, f"extension z-drop wb={wb}")
         n += 1
     assert n == 2

@@ -9,12 +9,6 @@ dispatches.  The oracle on skip-edge graphs is not pinned to the compiled refere
 read-sets at 30 % error at a band of the wide loop through the device-resident driver against the CPU build of the host layer (tests/cpu_shim.cpp, pinned to
 the reference's command-line tool at that band by tests/test_host_msa.py).  One launch per group of alignments that share a scoring; the oracle's planes of
 one (golden, width, band) are alive at a time (a convex alignment's planes at 704 columns are 16 MB).  Nothing here depends on timing."""
-import ctypes
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
@@ -22,18 +16,10 @@ import helpers as H
 import narrow_preds as NP
 import wide_bands as WB
 import wide_preds as WP
+from gpu_harness import dir_counts, engine, launch, words_match  # noqa: F401  (engine: the fixture)
+from readset_worker import run_report
 
 pytestmark = pytest.mark.gpu
-ROOT = H.ROOT
-
-
-@pytest.fixture(scope="module")
-def engine():
-    from abpoa_amd import ffi
-    lib = ffi.lib()
-    assert lib.abpoa_hip_device_count() >= 1, "no HIP device: the engine has no fallback"
-    ffi.check(lib.abpoa_hip_init(0))
-    return lib
 
 
 def _points():
@@ -77,26 +63,10 @@ def _launches(items):
     return list(groups.values())
 
 
-def _dir_counts(lib):
-    out = (ctypes.c_longlong * 2)()
-    lib.abpoa_hip__dir_counts(out)
-    return out[0], out[1]
-
-
 def _run(items, trace, label):
     """Every alignment against the oracle -- with the trace every plane cell, band and row arg-max too; one launch per scoring."""
     for group in _launches(items):
-        outs = H.run_hip([it[1] for it in group], want_trace=trace)
-        assert len(outs) == len(group)
-        for (name, c, _, o), h in zip(group, outs):
-            assert h.status == 0 and hasattr(h, "dp_beg") == trace and h.bits == o.bits, (label, name, h.status)
-            H.compare_outs(h, o, label=f"{label} {name} trace={trace}")
-
-
-def _words_match(items, label):
-    for name, c, d, _ in items:
-        bad = H.dir_words_mismatches(c, d)
-        assert bad is not None and bad == [], (label, name, bad[:5] if bad else bad)
+        launch(group, trace, label)
 
 
 def _point_items(key):
@@ -116,9 +86,9 @@ def test_record_walk_without_trace(engine, monkeypatch, key):
     """ABPOA_HIP_NODIR=1: the record walk (backtrack.h) over the slice windows of rows this wide -- behind the eighth predecessor on `jump`, over steps of 16 to
     300 rows on `farjump`, through the insertion runs of `ins`; no plane is walked."""
     monkeypatch.setenv("ABPOA_HIP_NODIR", "1")
-    _dir_counts(engine)
+    dir_counts(engine)
     _run(_point_items(key), False, f"records, no trace {key}")
-    assert _dir_counts(engine) == (0, 0)
+    assert dir_counts(engine) == (0, 0)
 
 
 @pytest.mark.parametrize("key", list(POINTS), ids=POINT_IDS)
@@ -127,9 +97,9 @@ def test_direction_words(engine, monkeypatch, key):
     walks the plane and none is redone with records."""
     monkeypatch.setenv("ABPOA_HIP_DIR_WIDE", "1")
     items = _point_items(key)
-    _dir_counts(engine)
+    dir_counts(engine)
     _run(items, False, f"words {key}")
-    assert _dir_counts(engine) == (len(items), 0), key
+    assert dir_counts(engine) == (len(items), 0), key
 
 
 @pytest.mark.parametrize("key", list(POINTS), ids=POINT_IDS)
@@ -137,7 +107,7 @@ def test_direction_words_match_the_model(engine, monkeypatch, key):
     """Every direction word the bodies write (trace mode with ABPOA_HIP_DIRTRACE=1) against the words oracle/dir_model.c derives from the oracle's scores: kM and
     kE up to 8 on the rows of five to eight predecessors, up to 11 on the rows general_body takes."""
     monkeypatch.setenv("ABPOA_HIP_DIR_WIDE", "1")
-    _words_match(_point_items(key), f"words against the model {key}")
+    words_match(_point_items(key), f"words against the model {key}")
 
 
 @pytest.mark.parametrize("key", BAND_POINTS, ids=BAND_IDS)
@@ -150,10 +120,10 @@ def test_four_row_ring(engine, monkeypatch, key):
     items = [_case(g, b, wb, f, "ring4") for f in WP.RING4_FAMILIES]
     _run(items, True, f"4-row ring {key}")
     monkeypatch.setenv("ABPOA_HIP_DIR_WIDE", "1")
-    _dir_counts(engine)
+    dir_counts(engine)
     _run(items, False, f"4-row ring, words {key}")
-    assert _dir_counts(engine) == (len(items), 0)
-    _words_match(items, f"4-row ring, words against the model {key}")
+    assert dir_counts(engine) == (len(items), 0)
+    words_match(items, f"4-row ring, words against the model {key}")
 
 
 @pytest.mark.parametrize("golden,bits", WP.COMBOS, ids=COMBO_IDS)
@@ -165,10 +135,10 @@ def test_448_column_kernel(engine, monkeypatch, golden, bits):
         items = [_case(golden, bits, wb, f, "noxl") for f in WP.NOXL_FAMILIES]
         _run(items, True, f"no long-read form wb={wb}")
         monkeypatch.setenv("ABPOA_HIP_DIR_WIDE", "1")
-        _dir_counts(engine)
+        dir_counts(engine)
         _run(items, False, f"no long-read form, words wb={wb}")
-        assert _dir_counts(engine) == (len(items), 0)
-        _words_match(items, f"no long-read form, words against the model wb={wb}")
+        assert dir_counts(engine) == (len(items), 0)
+        words_match(items, f"no long-read form, words against the model wb={wb}")
 
 
 @pytest.mark.parametrize("bt_bytes", WP.BT_BYTES)
@@ -180,13 +150,13 @@ def test_small_backtrack_windows(engine, monkeypatch, golden, bits, bt_bytes):
     wb = WP.BT_BAND[bits]
     items = [_case(golden, bits, wb, f, "bt") for f in WP.WALK_FAMILIES]
     monkeypatch.setenv("ABPOA_HIP_DIR_WIDE", "1")
-    _dir_counts(engine)
+    dir_counts(engine)
     _run(items, False, f"small windows, words {golden} int{bits}")
-    assert _dir_counts(engine) == (len(items), 0)
+    assert dir_counts(engine) == (len(items), 0)
     monkeypatch.delenv("ABPOA_HIP_DIR_WIDE")
     monkeypatch.setenv("ABPOA_HIP_NODIR", "1")
     _run(items, False, f"small windows, records {golden} int{bits}")
-    assert _dir_counts(engine) == (0, 0)
+    assert dir_counts(engine) == (0, 0)
 
 
 @pytest.mark.parametrize("golden", WP.GOLDENS)
@@ -200,20 +170,16 @@ def test_mixed_launch(engine, monkeypatch, golden):
         d["wf"] = np.array([m["wf"]], np.float32)
         items.append((f, H.FlatCase(d)))
     items = items[3:] + items[:3]                  # (the short one in the middle)
-    oracle = {name: H.run_oracle(c) for name, c in items}
-    assert all(o.status == 0 and o.bits == 16 for o in oracle.values())
+    items = [(name, c, H.run_oracle(c)) for name, c in items]
+    assert all(o.status == 0 and o.bits == 16 for _, _, o in items)
     for order in (items, items[::-1]):
-        outs = H.run_hip([c for _, c in order], want_trace=True)
-        for (name, _), h in zip(order, outs):
-            H.compare_outs(h, oracle[name], label=f"mixed launch {golden} {name}")
-    for o in oracle.values():
+        launch(order, True, f"mixed launch {golden}")
+    for _, _, o in items:
         o.planes = None
     monkeypatch.setenv("ABPOA_HIP_DIR_WIDE", "1")
-    _dir_counts(engine)
-    outs = H.run_hip([c for _, c in items], want_trace=False)
-    for (name, _), h in zip(items, outs):
-        H.compare_outs(h, oracle[name], label=f"mixed launch, words {golden} {name}")
-    assert _dir_counts(engine) == (len(items), 0)
+    dir_counts(engine)
+    launch(items, False, f"mixed launch, words {golden}")
+    assert dir_counts(engine) == (len(items), 0)
 
 
 @pytest.mark.parametrize("golden", WP.GOLDENS)
@@ -226,65 +192,26 @@ def test_extension_mode_with_zdrop(engine, golden):
         o = H.run_oracle(c)
         assert o.status == 0
         for trace in (True, False):
-            h = H.run_hip([c], want_trace=trace)[0]
-            assert h.status == 0 and hasattr(h, "dp_beg") == trace
-            H.compare_outs(h, o, label=f"extension z-drop {golden} {f} trace={trace}")
+            h = launch([(f, c, o)], trace, f"extension z-drop {golden}")[0]
             assert (h.best_score, h.best_row, h.best_col) == (o.best_score, o.best_row, o.best_col)
             if trace:
                 assert np.array_equal(h.dp_beg_sn < 0, o.dp_beg_sn < 0), (golden, f)
 
 
 # ---------------------------------------------------------------- read-sets at a band of the wide loop through the device-resident driver
-_WORKER = r"""
-import ctypes, json, os, sys
-sys.path.insert(0, %(root)r); sys.path.insert(0, os.path.join(%(root)r, 'tests'))
-import numpy as np
-import helpers as H, narrow_preds as T, wide_preds as WP
-from abpoa_amd import api, ffi, seqio
-def digests(lib, sets, m):
-    lib.abpoa_hip__cigar_digest.restype = ctypes.c_ulonglong
-    out = []
-    for s in sets:
-        a = np.ascontiguousarray(seqio.encode(s[0], m), np.uint8)
-        out.append(int(lib.abpoa_hip__cigar_digest(a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), len(a), 0)))
-    lib.abpoa_hip__cigar_digest(None, 0, 1)
-    return out
-def record(res, dig):
-    return dict(status=[r.status for r in res], cons=[r.cons_seq for r in res], cov=[list(map(int, r.cons_cov)) for r in res], n_cells=[int(r.n_cells) for r in res],
-                msa=[list(r.msa_seq) for r in res], dig=dig)
-lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0)); shim = H.cpu_shim_lib()
-launches = (ctypes.c_longlong * 3)()
-report = {}
-for gaps, kw in (('affine', T.AFFINE), ('convex', WP.CONVEX)):
-    p = api.Params(**kw, **WP.READ_SET_BAND)
-    for kind in T.KINDS:
-        sets = T.read_sets(kind)
-        rep = {}
-        ref = api.msa_batch(sets, p, out_msa=True, n_threads=4, lib=shim)
-        rep['shim'] = record(ref, digests(shim, sets, p.m))
-        for form, env in WP.READ_SET_FORMS.items():
-            for k, v in env.items(): os.environ[k] = v
-            lib.abpoa_hip__row_launches(launches)
-            res = api.msa_batch(sets, p, out_msa=True, n_threads=4)
-            lib.abpoa_hip__row_launches(launches)
-            rep[form] = record(res, digests(lib, sets, p.m))
-            rep[form]['n_host_sets'] = int(api.msa_timing()['n_host_sets']); rep[form]['host_reasons'] = api.host_reasons()
-            rep[form]['launches'] = [int(x) for x in launches]
-            for k in env: del os.environ[k]
-        report[gaps + '/' + kind] = rep
-print('REPORT ' + json.dumps(report))
-"""
+def make_jobs():
+    """{"<gaps>/<kind>": spec} for tests/readset_worker.py: the read-sets of tests/narrow_preds.py at READ_SET_BAND, affine and convex, in every form."""
+    fields = ("n_cells", "msa", "dig")
+    return {f"{gaps}/{kind}": dict(params=dict(kw, **WP.READ_SET_BAND), sets=NP.read_sets(kind), forms=WP.READ_SET_FORMS, ref_first=True,
+                                   record=fields + ("launches", "n_host_sets", "host_reasons"), ref_record=fields)
+            for gaps, kw in (("affine", NP.AFFINE), ("convex", WP.CONVEX)) for kind in NP.KINDS}
 
 
 @pytest.fixture(scope="module")
 def report():
-    env = dict(os.environ, ABPOA_HIP_CIGAR_DIGEST="1")
-    for k in ("ABPOA_HIP_DBG", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_DEVSYNC", "ABPOA_HIP_NODIR", "ABPOA_HIP_VERBOSE", "ABPOA_HIP_DIR_WIDE", "ABPOA_HIP_RING_ROWS"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-c", _WORKER % dict(root=ROOT)], capture_output=True, text=True, env=env, timeout=600)
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("REPORT ")]
-    assert r.returncode == 0 and lines, (r.stdout[-1500:], r.stderr[-3000:])
-    return json.loads(lines[0][7:])
+    return run_report("test_gpu_wide_pred_bodies", set_env={"ABPOA_HIP_CIGAR_DIGEST": "1"}, timeout=600,
+                      clear_env=("ABPOA_HIP_DBG", "ABPOA_HIP_LOCKSTEP", "ABPOA_HIP_DEVSYNC", "ABPOA_HIP_NODIR", "ABPOA_HIP_VERBOSE", "ABPOA_HIP_DIR_WIDE",
+                                 "ABPOA_HIP_RING_ROWS"))
 
 
 @pytest.mark.parametrize("kind", list(NP.KINDS))
@@ -295,7 +222,7 @@ def test_device_driver_on_divergent_read_sets_at_a_wide_band(report, gaps, kind)
     rows, n_cells and cigar digests equal the CPU shim's; no set leaves the device; the wide row kernels were launched and the narrow one never was
     (abpoa_hip__row_launches, counted where the kernels are launched)."""
     rep = report[f"{gaps}/{kind}"]
-    ref = rep["shim"]
+    ref = rep["ref"]
     assert all(s == 0 for s in ref["status"]) and all(d != 0 for d in ref["dig"]) and len(ref["status"]) == NP.N_SETS[kind]
     for form in WP.READ_SET_FORMS:
         got = rep[form]
