@@ -5,7 +5,7 @@ namespace abpoa_hip {
 
 // Everything after the row loop: global best (reference :1028-1041), backtrack (:109-429) and the result record.  Shared by the
 // general kernel and the fast-loop kernel; reads only what the row loops left in HBM (planes, per-row band geometry).
-struct TailState { long long cursor, n_cells, clk0, clk1, seg[6]; int status, rows_done, best_score, best_i, best_j; };
+struct TailState { long long cursor, n_cells, clk0, clk1, seg[DIAG_SLOTS]; int status, rows_done, best_score, best_i, best_j; };
 
 // CW = 0: plane-major arena rows (general kernel); CW > 0: cell records of CW values (fast loop, see rows_fast)
 template <typename T, int GAP, int CW = 0>
@@ -626,14 +626,14 @@ __device__ __forceinline__ void finish_alignment(const DevBatch &b, const AlnDes
         }
     }
     if (lane == 0) {
-        AlnOut o; for (int i_ = 0; i_ < 6; ++i_) o.seg[i_] = 0;
+        AlnOut o; for (int i_ = 0; i_ < DIAG_SLOTS; ++i_) o.seg[i_] = 0;
         o.status = status; o.best_score = best_score; o.best_row = best_i; o.best_col = best_j;
         o.node_s = node_s; o.node_e = node_e; o.query_s = query_s; o.query_e = query_e;
         o.n_aln_bases = n_aln; o.n_matched_bases = n_match; o.n_cigar = n_cigar; o.pad = CW;      // pad = arena cell stride (0: plane-major)
         o.n_cells = n_cells; o.cells_used = cursor;
-        for (int i_ = 0; i_ < 6; ++i_) o.seg[i_] = seg[i_];
-        // (dbg bit 7: keep the row loop's counters) backtrack: ticks spent staging arena windows, number of windows
-        if (!(b.dbg & 128)) { o.seg[5] = bt_win_ticks; o.seg[4] = bt_n_windows * 1000; o.seg[3] = bt_slow_steps * 1000; o.seg[0] = bt_wa; o.seg[1] = bt_wb; o.seg[2] = bt_flag_steps * 1000; }
+        for (int i_ = 0; i_ < DIAG_SLOTS; ++i_) o.seg[i_] = seg[i_];
+        if (!(b.dbg & DBG_KEEP_ROW_SLOTS)) { o.seg[RTAIL_WINDOW_TICKS] = bt_win_ticks; o.seg[RTAIL_WINDOWS_K] = bt_n_windows * 1000; o.seg[RTAIL_SLOW_STEPS_K] = bt_slow_steps * 1000;
+                o.seg[RTAIL_SETUP_TICKS] = bt_wa; o.seg[RTAIL_WALK_TICKS] = bt_wb; o.seg[RTAIL_FLAG_STEPS_K] = bt_flag_steps * 1000; }
         o.clk_dp = clk1 - clk0; o.clk_bt = (long long)__builtin_amdgcn_s_memtime() - clk1; o.n_rows_done = rows_done; o.n_bt_steps = bt_steps;
         *out_rec = o;
     }

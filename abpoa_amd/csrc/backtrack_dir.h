@@ -239,7 +239,7 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
     int n_cigar = 0, node_s = 0, node_e = 0, query_s = 0, query_e = 0, n_aln = 0, n_match = 0;
     lds_vint_t *fp = ctl + SPEC_FP; bool fp_told = false;      // the word that sends the helpers into the final pass, or home (helper_final_pass)
     long long win_ticks = 0, walk_ticks = 0; int n_windows = 0, n_general = 0;
-    long long dbg_why = 0, dbg_a = 0, dbg_b = 0;      // (dead end of the walk: where and on what, for AlnOut.seg under ABPOA_HIP_DBG bit 8)
+    long long dbg_why = 0, dbg_a = 0, dbg_b = 0;      // (dead end of the walk: where and on what, for the walk report in AlnOut.seg: DBG_WALK_REPORT)
     if (spec_static && role == 0 && !early) {      // late start: clear the tables, then let the helpers go (whatever the row loop's status: they wait for this)
         for (int t = lane; t < (SPEC_WK - 1) * SPEC_PM_ROWS; t += 64) pm_all[t] = 0;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -536,8 +536,8 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
                         if (GAP == 1) { kMl = wl & 15; uEl0 = 0; uEl1 = 0; dFl = (wl >> DIRA_DF1_SH) & 7; }
                         else { kMl = wl & 15; uEl0 = (wl >> DIRC_UE1_SH) & 7; uEl1 = (wl >> DIRC_UE2_SH) & 31; dFl = x == 0 ? (wl >> DIRC_DF1_SH) & 7 : (wl >> DIRC_DF2_SH) & 31; }
                         const int h_is_hv = kMl != 0 || (GAP == 2 && (uEl0 == o1 || uEl1 == o2));
-                        // the plane cannot decide this one (dir_plane.h); dbg bit 9: at the first insertion decided from the words (tests of the redo path)
-                        if ((!h_is_hv && dFl > ox) || (b.dbg & 512)) { status = ABPOA_HIP_STATUS_NEED_SCORES; break; }
+                        // the plane cannot decide this one (dir_plane.h); DBG_WALK_GIVES_UP: at the first insertion decided from the words (tests of the redo path)
+                        if ((!h_is_hv && dFl > ox) || (b.dbg & DBG_WALK_GIVES_UP)) { status = ABPOA_HIP_STATUS_NEED_SCORES; break; }
                         lit = dir_f_origin(h_is_hv, dFl, ox);
                     }
                     if (lit == DIR_LIT_OPEN) { cur_op = OP_M | OP_E; hit = 1; }
@@ -613,14 +613,15 @@ __device__ __forceinline__ void finish_alignment_dir(const DevBatch &b, const Al
     }
     if (spec_static && role == 0 && !fp_told) { if (lane == 0) fp[0] = gen << 1; }      // (2) of the list at helper_final_pass: no pass this round
     if (lane == 0) {
-        AlnOut o; for (int i_ = 0; i_ < 6; ++i_) o.seg[i_] = ts.seg[i_];
+        AlnOut o; for (int i_ = 0; i_ < DIAG_SLOTS; ++i_) o.seg[i_] = ts.seg[i_];
         o.status = status; o.best_score = best_score; o.best_row = best_i; o.best_col = best_j;
         o.node_s = node_s; o.node_e = node_e; o.query_s = query_s; o.query_e = query_e;
         o.n_aln_bases = n_aln; o.n_matched_bases = n_match; o.n_cigar = n_cigar; o.pad = -DB;      // pad < 0: direction-plane arena (bytes per word)
         o.n_cells = ts.n_cells; o.cells_used = ts.cursor;
-        if (b.dbg & 256) { o.seg[0] = dbg_why; o.seg[1] = dbg_a; o.seg[2] = dbg_b; o.seg[3] = ((long long)best_i << 32) | (unsigned)best_j; o.seg[4] = n_cigar; o.seg[5] = bt_steps; }
-        else if (!(b.dbg & 128)) { o.seg[5] = win_ticks; o.seg[4] = (long long)n_windows * 1000; o.seg[3] = (long long)n_general * 1000; o.seg[0] = 0; o.seg[1] = walk_ticks;
-                o.seg[2] = (long long)bt_steps * 1000; }
+        if (b.dbg & DBG_WALK_REPORT) { o.seg[WALK_WHY] = dbg_why; o.seg[WALK_A] = dbg_a; o.seg[WALK_B] = dbg_b; o.seg[WALK_BEST] = ((long long)best_i << 32) | (unsigned)best_j;
+                o.seg[WALK_N_CIGAR] = n_cigar; o.seg[WALK_STEPS] = bt_steps; }
+        else if (!(b.dbg & DBG_KEEP_ROW_SLOTS)) { o.seg[DTAIL_WINDOW_TICKS] = win_ticks; o.seg[DTAIL_WINDOWS_K] = (long long)n_windows * 1000; o.seg[DTAIL_GENERAL_STEPS_K] = (long long)n_general * 1000;
+                o.seg[DTAIL_ZERO] = 0; o.seg[DTAIL_WALK_TICKS] = walk_ticks; o.seg[DTAIL_STEPS_K] = (long long)bt_steps * 1000; }
         o.clk_dp = ts.clk1 - ts.clk0; o.clk_bt = (long long)__builtin_amdgcn_s_memtime() - ts.clk1; o.n_rows_done = ts.rows_done; o.n_bt_steps = bt_steps;
         *out_rec = o;
     }

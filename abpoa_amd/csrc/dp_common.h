@@ -259,7 +259,7 @@ template <> __device__ __forceinline__ int inj_dist<8>(int l) { return l < 4 ? 0
 // then max-plus arithmetic distributes and  F[l] = max( scan of the vector's own H , first - oe - l*e , inf - INJ[l]*e ),
 // and the vector-to-vector carry is first' = max(H[pn-1], ownscan[pn-1] + o, first - pn*e).  Plain int arithmetic.
 template <typename T>
-__device__ __forceinline__ int fast_f_chain(int hs, int &first, int nfast, int l, int vvl, int oe, int e, int o, int cl, int inj, int *dbg_cv = nullptr) {
+__device__ __forceinline__ int fast_f_chain(int hs, int &first, int nfast, int l, int vvl, int oe, int e, int o, int cl, int inj) {
     constexpr int PN = Width<T>::PN, NV = 64 / PN;
     int f = row_shr<1>(hs, hs) - oe;                 // own sources: F0[l] = H[l-1] - oe for l >= 1 (lane 0 has none)
     if (PN == 16) {
@@ -275,7 +275,6 @@ __device__ __forceinline__ int fast_f_chain(int hs, int &first, int nfast, int l
         t = row_shr<4>(f, f) - 4 * e; f = (l > 4) ? imax(f, t) : f;
     }
     const int cv = imax(hs, f + o);                  // at lane pn-1 of a vector: max(H[pn-1], ownscan[pn-1] + o)
-    if (dbg_cv) *dbg_cv = cv;
     int fc[NV + 1]; fc[0] = first;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {

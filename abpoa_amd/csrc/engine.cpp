@@ -56,7 +56,7 @@ struct Engine {
     std::mutex mu, stats_mu;
 };
 static Engine g;
-long long g_dbg[10] = {0};
+long long g_dbg[CLK_SLOTS] = {0};      // (abpoa_hip__debug_clocks; slots: diag.h)
 long long g_dir_counts[2] = {0, 0};      // alignments whose backtrack walked a direction plane; alignments redone with score records (NEED_SCORES)
 long long g_row_launches[3] = {0, 0, 0}; // launches of the narrow row kernel, of dp_wide_kernel, of dp_xl_kernel (launch_dp_fast counts, abpoa_hip__row_launches reads)
 
@@ -311,7 +311,8 @@ int BatchStream::run() {
             }
             stats_.n_alignments += 1; stats_.n_cells += r.n_cells;
             stats_.algo_bytes += r.n_cells * (d.bits / 8) * (P == 1 ? 2 : (P == 3 ? 5 : 8));
-            g_dbg[0] += r.clk_dp; g_dbg[1] += r.clk_bt; g_dbg[2] += r.n_rows_done; g_dbg[3] += r.n_bt_steps; for (int q_ = 0; q_ < 6; ++q_) g_dbg[4 + q_] += r.seg[q_];
+            g_dbg[CLK_DP] += r.clk_dp; g_dbg[CLK_BT] += r.clk_bt; g_dbg[CLK_ROWS_DONE] += r.n_rows_done; g_dbg[CLK_BT_STEPS] += r.n_bt_steps;
+            for (int q_ = 0; q_ < DIAG_SLOTS; ++q_) g_dbg[CLK_SEG0 + q_] += r.seg[q_];
         }
         todo.swap(again); first_pass = false;
         if (need_scores) dir = false;                 // the retry pass runs with score records (full width: simplest, and rare)
@@ -428,7 +429,7 @@ void abpoa_hip__narrow_plan(const abpoa_hip_scoring_t *sc, int max_qlen, int max
 }
 // (test hook, host only, read-only for the engine: row-kernel launches since the last call -- narrow loop, 448-column wide loop, 704-column wide loop)
 void abpoa_hip__row_launches(long long *out) { for (int i = 0; i < 3; ++i) out[i] = __atomic_exchange_n(&abpoa_hip::g_row_launches[i], 0, __ATOMIC_RELAXED); }
-void abpoa_hip__debug_clocks(long long *out) { for (int i = 0; i < 10; ++i) { out[i] = g_dbg[i]; g_dbg[i] = 0; } }
+void abpoa_hip__debug_clocks(long long *out) { for (int i = 0; i < CLK_SLOTS; ++i) { out[i] = g_dbg[i]; g_dbg[i] = 0; } }
 void abpoa_hip_reset_stats(void) { std::lock_guard<std::mutex> lk(g.stats_mu); memset(&g.stats, 0, sizeof(g.stats)); }
 
 void abpoa_hip_free_result(abpoa_hip_result_t *r) {

@@ -7,6 +7,7 @@
 #include "dir_plane.h"
 #include "device_codes.h"
 #include "engine_options.h"
+#include "diag.h"
 
 namespace abpoa_hip {
 
@@ -41,7 +42,8 @@ struct AlnOut {
     int64_t cells_used;   // arena cells consumed (all rows incl. row 0, all planes)
     int64_t clk_dp, clk_bt; // shader-clock ticks spent in the row loop / in the backtrack (s_memtime)
     int32_t n_rows_done, n_bt_steps;
-    int64_t seg[6];       // ABPOA_HIP_PROFILE builds: ticks per row-loop segment
+    int64_t seg[DIAG_SLOTS];   // diagnostics, one layout at a time (diag.h): the row loop's by its build (placement | profile segments | narrow census |
+                          // wide counters), then the tail's (direction-word | record tail) unless dbg keeps the former or asks for the walk report
 };
 
 #define ALN_FAST_OK 1
@@ -93,7 +95,8 @@ struct DevBatch {
     int32_t o1, e1, o2, e2;
     int32_t align_mode, gap_mode, wb, zdrop, ret_cigar, rev_cigar;
     int32_t want_trace;          // also record the per-row arg-max column (tests)
-    int32_t dbg;                 // ablation switches for timing experiments (env ABPOA_HIP_DBG); 0 in production
+    int32_t dbg;                 // env ABPOA_HIP_DBG, the DBG_* bits of diag.h: test hooks and report selectors, which change no result; its timing ablations
+                                 // (bits 0-5, results wrong on purpose) are compiled into `make prof` libraries only
     int32_t fresh_band;          // max_pos_left/right start as (n_rows, 0): initialise them on the device
     int32_t want_lr;             // the caller reads max_pos_left/right back (the fast row loop derives them in a post-pass)
     int32_t bits_mask;           // score widths that may occur among the fast alignments: 1 = int16, 2 = int32, 3 = both (one kernel per width)

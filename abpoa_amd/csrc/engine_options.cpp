@@ -1,4 +1,5 @@
 #include "engine_options.h"
+#include "diag.h"
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -9,6 +10,10 @@ namespace abpoa_hip {
 namespace {
 
 struct Row { const char *name, *help; };
+// the help of ABPOA_HIP_DBG names every bit diag.h defines
+const std::string kDbgHelp = [] { std::string h = "D  bit mask handed to the kernels (DevBatch.dbg; diag.h):";
+                                  for (const DbgBit &d : DBG_BITS) h += (&d == DBG_BITS ? " " : ", ") + std::to_string(d.value) + " " + d.what;
+                                  return h; }();
 // P: product switches (documented in INTEGRATION.md); T: test hooks (force a code path that the engine otherwise picks by itself); D: diagnostics
 const Row kTable[] = {
     {"ABPOA_GPU_DEVICES", "P  device ordinals abpoa_hip_msa_batch spreads its batches over: all | 0,1,... (default: the device of abpoa_hip_init)"},
@@ -42,7 +47,7 @@ const Row kTable[] = {
     {"ABPOA_HIP_BT_WC", "T  columns per row of the tail's column-slice windows"},
     {"ABPOA_HIP_ORDER_LDS", "T  0: the row-order walk with global tables"},
     {"ABPOA_HIP_ORDER_CAP", "T  node capacity of the row-order walk's LDS tables"},
-    {"ABPOA_HIP_DBG", "D  bit mask handed to the kernels (DevBatch.dbg: 64 no fast loops, 128 keep counters, 1024 one wavefront per backtrack, 2048 the compiler's tight loop, ...)"},
+    {"ABPOA_HIP_DBG", kDbgHelp.c_str()},
     {"ABPOA_HIP_DEVSYNC", "D  1: compare device graph / row order / MSA with the host's after every read"},
     {"ABPOA_HIP_DEVICE_AUDIT", "D  1: every pool of a device queue must sit on that queue's device"},
     {"ABPOA_HIP_CIGAR_DIGEST", "D  1: fold every graph cigar into a per-set digest on the device"},

@@ -332,7 +332,7 @@ int fill_dev_batch(Job &J, bool *want_general) {
     if (!pl.local && !pl.general && !fast_loop_fits(b.lds, pl.max_qlen)) { *want_general = true; set_err("band too wide for the fast row loop"); return ABPOA_HIP_EINVAL; }
     set_job_fields(b, *sc); b.ret_cigar = 1; b.rev_cigar = 0;
     b.want_trace = 0; b.fresh_band = 1; b.want_lr = 0;
-    b.dbg = opt_int("ABPOA_HIP_DBG", 0);      // (diagnostics: bit 7 keeps the row loop's counters in AlnOut.seg)
+    b.dbg = opt_int("ABPOA_HIP_DBG", 0);      // (diag.h)
     b.mat = (const int32_t *)(di + L.o_mat); b.aln = p.aln; b.out = p.out;
     b.dir_mode = pl.dir ? (pl.dir_wide ? 2 : 1) : 0; b.row_sdist = p.row_sdist; b.row_pd = p.row_pd;
     b.query = p.reads; b.row_base = p.row_base; b.row_node_id = p.row_node_id; b.row_remain = p.row_remain; b.row_active = p.row_base;
@@ -361,7 +361,7 @@ void plan_rounds(Job &J) {
     const DevicePlan &pl = J.pl; const abpoa_hip_scoring_t *sc = &pl.sc; const PoaDev &p = J.p; const DevBatch &b = J.b; DevBatch &b_r = J.b_r;
     bool &dbg_sync = J.dbg_sync, &use_rounds = J.use_rounds; size_t &rounds_lds = J.rounds_lds;
     dbg_sync = opt_on("ABPOA_HIP_DEVSYNC");
-    use_rounds = !pl.local && pl.rounds_possible && !dbg_sync && b.lds.wide_on == 0 && !(b.dbg & 64) && pl.max_reads > 2 && !opt_on("ABPOA_HIP_LOCKSTEP");
+    use_rounds = !pl.local && pl.rounds_possible && !dbg_sync && b.lds.wide_on == 0 && !(b.dbg & DBG_NO_FAST_LOOPS) && pl.max_reads > 2 && !opt_on("ABPOA_HIP_LOCKSTEP");
     b_r = b; rounds_lds = 0;
     if (use_rounds) {
         // (prepare: 5 bytes per row; fuse: static LDS only)

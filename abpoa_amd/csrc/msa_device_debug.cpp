@@ -248,7 +248,7 @@ void DeviceDebug::balance_report(int k, const DevBatch &b, hipEvent_t rows_begin
     if (k == max_reads - 1) { double mx_ = 0, mean_ = 0; for (double v_ : tot_set) { mx_ = std::max(mx_, v_); mean_ += v_; } fprintf(stderr,
             "[poa-device] rows+tail ticks over all rounds: sum of per-round maxima %.0f | slowest set alone %.0f | mean set %.0f\n", sum_max, mx_,
             mean_ / n_sets); }
-    double sg[6] = {0, 0, 0, 0, 0, 0}, st_ = 0; for (const AlnOut &o_ : ho) { for (int q_ = 0; q_ < 6; ++q_) sg[q_] += o_.seg[q_]; st_ += o_.n_bt_steps; }
+    double sg[DIAG_SLOTS] = {0, 0, 0, 0, 0, 0}, st_ = 0; for (const AlnOut &o_ : ho) { for (int q_ = 0; q_ < DIAG_SLOTS; ++q_) sg[q_] += o_.seg[q_]; st_ += o_.n_bt_steps; }
     // (direction-plane arenas: how much of them is score records of rows kept for later readers)
     if (b.dir_mode) { double cu = 0, nc = 0, rd = 0; for (const AlnOut &o_ : ho) { cu += (double)o_.cells_used; nc += (double)o_.n_cells; rd += o_.n_rows_done;
             }
@@ -256,11 +256,12 @@ void DeviceDebug::balance_report(int k, const DevBatch &b, hipEvent_t rows_begin
                               "[poa-device] round %d arenas: %.0f rows, %.0f columns, %.0f units of 32 B per alignment; words alone "
                                       "would take %.0f (int16 affine) -> rows keeping their records: ~%.1f %%\n", k, rd / n_sets, nc / n_sets,
                                       cu / n_sets / 16, nc / n_sets / 16, 100.0 * (cu - nc) / (4.0 * nc + 1)); }
-    // placement report (row-loop seg[5] = HW_ID | XCC_ID << 32 survives the tail under dbg bit 7): how many alignments shared a SIMD, and how the sharers fared
-    if (b.dbg & 128) {
-        // xcc | se, sh, cu | simd
-        std::vector<std::pair<unsigned long long, int>> pl; for (int s_ = 0; s_ < n_sets; ++s_) { const unsigned long long h_ =
-                (unsigned long long)ho[s_].seg[5]; pl.push_back({((h_ >> 32) & 15) << 16 | (h_ & 0xff30) , s_}); }
+    // What AlnOut.seg holds is chosen by the library's build and by b.dbg (diag.h): with DBG_KEEP_ROW_SLOTS the row loop's layout survives the tail.
+    const bool row_slots = (b.dbg & DBG_KEEP_ROW_SLOTS) != 0;
+    int slowest = 0; for (int s_ = 0; s_ < n_sets; ++s_) if (ho[s_].clk_dp > ho[slowest].clk_dp) slowest = s_;
+    // placement report: how many alignments shared a SIMD, and how the sharers fared
+    if (row_slots) {
+        std::vector<std::pair<unsigned long long, int>> pl; for (int s_ = 0; s_ < n_sets; ++s_) pl.push_back({placement_simd(ho[s_].seg[PLACE_KEY]), s_});
         std::sort(pl.begin(), pl.end()); double t_sh = 0, t_al = 0; int n_sh = 0, n_al = 0;
         for (size_t i_ = 0; i_ < pl.size(); ++i_) { const bool sh_ = (i_ > 0 && pl[i_ - 1].first == pl[i_].first) || (i_ + 1 < pl.size() && pl[i_
                 + 1].first == pl[i_].first); (sh_ ? t_sh : t_al) += (double)ho[pl[i_].second].clk_dp; (sh_ ? n_sh : n_al)++; }
@@ -268,44 +269,44 @@ void DeviceDebug::balance_report(int k, const DevBatch &b, hipEvent_t rows_begin
                 n_al ? t_al / n_al : 0.0, n_sh, n_sh ? t_sh / n_sh : 0.0);
     }
     // (library built with -DABPOA_HIP_ROW_CENSUS) rows and ticks per body of the narrow row loop, mean per alignment
-    if ((b.dbg & 128) && opt_set("ABPOA_HIP_ROW_CENSUS")) {
-        double rw[6] = {0, 0, 0, 0, 0, 0}, tk[6] = {0, 0, 0, 0, 0, 0}; for (const AlnOut &o_ : ho) for (int q_ = 0; q_ < 6; ++q_) {
-                rw[q_] += (double)(o_.seg[q_] >> 40); tk[q_] += (double)(o_.seg[q_] & ((1ll << 40) - 1)); }
-        // (a build with -DABPOA_HIP_ASM_CENSUS as well: slot 0 = the rows of the assembly loop, slot 1 = the C++ copies of the one- / two-predecessor body)
-        const bool asmc_ = opt_int("ABPOA_HIP_ROW_CENSUS", 0) == 2;
-        const char *nm_[5] = {asmc_ ? "assembly loop" : "1 predecessor", asmc_ ? "C++ 1-2 predecessors" : "2 predecessors", "3-8 predecessors (C++)", "all-chunks / exact bodies", "tile switches"};
+    if (row_slots && opt_set("ABPOA_HIP_ROW_CENSUS")) {
+        double rw[CEN_WHY] = {0, 0, 0, 0, 0}, tk[CEN_WHY] = {0, 0, 0, 0, 0}, why[3] = {0, 0, 0};
+        for (const AlnOut &o_ : ho) { for (int q_ = 0; q_ < CEN_WHY; ++q_) { rw[q_] += (double)census_rows(o_.seg[q_]); tk[q_] += (double)census_ticks(o_.seg[q_]); }
+                why[0] += (double)census_why_many_preds(o_.seg[CEN_WHY]); why[1] += (double)census_why_declined(o_.seg[CEN_WHY]); why[2] += (double)census_why_beyond_ring(o_.seg[CEN_WHY]); }
+        const bool asmc_ = opt_int("ABPOA_HIP_ROW_CENSUS", 0) == 2;      // (a build with -DABPOA_HIP_ASM_CENSUS as well: CEN_ASM_LOOP, CEN_CXX_TIGHT)
+        const char *nm_[CEN_WHY] = {asmc_ ? "assembly loop" : "1 predecessor", asmc_ ? "C++ 1-2 predecessors" : "2 predecessors", "3-8 predecessors (C++)", "all-chunks / exact bodies", "tile switches"};
         fprintf(stderr, "[poa-device] round %d narrow-loop census per alignment:", k);
-        for (int q_ = 0; q_ < 5; ++q_) fprintf(stderr, " %s %.0f x %.0f ticks |", nm_[q_], rw[q_] / n_sets, rw[q_] > 0 ? tk[q_] / rw[q_] : 0.0);
-        { int w_ = 0; for (int s_ = 0; s_ < n_sets; ++s_) if (ho[s_].clk_dp > ho[w_].clk_dp) w_ = s_; const AlnOut &o_ = ho[w_];
-          fprintf(stderr, "\n[poa-device] round %d slowest row loop (set %d, %lld ticks):", k, w_, (long long)o_.clk_dp);
-          for (int q_ = 0; q_ < 5; ++q_) fprintf(stderr, " %s %lld x %.0f |", nm_[q_], (long long)(o_.seg[q_] >> 40), (o_.seg[q_] >> 40)
-                  ? (double)(o_.seg[q_] & ((1ll << 40) - 1)) / (double)(o_.seg[q_] >> 40) : 0.0);
-          fprintf(stderr, " exact-body rows: > 4 predecessors %lld, straight-line declined %lld, beyond the ring %lld;", (long long)(o_.seg[5] >> 40),
-                  (long long)((o_.seg[5] >> 20) & 0xfffff), (long long)(o_.seg[5] & 0xfffff)); }
-        double why[3] = {0, 0, 0}; for (const AlnOut &o_ : ho) { why[0] += (double)(o_.seg[5] >> 40); why[1] += (double)((o_.seg[5] >> 20) & 0xfffff);
-                why[2] += (double)(o_.seg[5] & 0xfffff); }
+        for (int q_ = 0; q_ < CEN_WHY; ++q_) fprintf(stderr, " %s %.0f x %.0f ticks |", nm_[q_], rw[q_] / n_sets, rw[q_] > 0 ? tk[q_] / rw[q_] : 0.0);
+        { const AlnOut &o_ = ho[slowest];
+          fprintf(stderr, "\n[poa-device] round %d slowest row loop (set %d, %lld ticks):", k, slowest, (long long)o_.clk_dp);
+          for (int q_ = 0; q_ < CEN_WHY; ++q_) fprintf(stderr, " %s %lld x %.0f |", nm_[q_], census_rows(o_.seg[q_]), census_rows(o_.seg[q_])
+                  ? (double)census_ticks(o_.seg[q_]) / (double)census_rows(o_.seg[q_]) : 0.0);
+          fprintf(stderr, " exact-body rows: > 4 predecessors %lld, straight-line declined %lld, beyond the ring %lld;", census_why_many_preds(o_.seg[CEN_WHY]),
+                  census_why_declined(o_.seg[CEN_WHY]), census_why_beyond_ring(o_.seg[CEN_WHY])); }
         fprintf(stderr, " exact-body rows: > 4 predecessors %.0f, straight-line body declined %.0f, predecessor beyond the ring %.0f\n", why[0] / n_sets,
                 why[1] / n_sets, why[2] / n_sets);
     }
-    if ((b.dbg & 128) && opt_set("ABPOA_HIP_WIDE_COUNTERS")) { int w_ = 0; for (int s_ = 0; s_ < n_sets; ++s_) if (ho[s_].clk_dp > ho[w_].clk_dp) w_ = s_;
-            const AlnOut &o_ = ho[w_];
+    // (library built with -DABPOA_HIP_WIDE_COUNTERS) rows per path of the wide loop
+    if (row_slots && opt_set("ABPOA_HIP_WIDE_COUNTERS")) { const AlnOut &o_ = ho[slowest];
         fprintf(stderr,
                 "[poa-device] round %d slowest row loop: set %d ticks %lld rows %d | all-chunk body %lld | not eligible "
-                        "%lld | ring-geometry %lld | > 5 chunks %lld | slow vectors straddle %lld | key window / wrap %lld\n", k, w_, (long long)o_.clk_dp,
-                        o_.n_rows_done, (long long)(o_.seg[0] & 0xffffffffll), (long long)o_.seg[1], (long long)o_.seg[2], (long long)o_.seg[3], (long long)o_.seg[4],
-                        (long long)o_.seg[5]); }
+                        "%lld | ring-geometry %lld | > 5 chunks %lld | slow vectors straddle %lld | key window / wrap %lld\n", k, slowest, (long long)o_.clk_dp,
+                        o_.n_rows_done, wide_body_rows(o_.seg[WC_BODY]), (long long)o_.seg[WC_NOT_ELIGIBLE], (long long)o_.seg[WC_RING_GEOMETRY], (long long)o_.seg[WC_TOO_WIDE],
+                        (long long)o_.seg[WC_STRADDLE], (long long)o_.seg[WC_DECLINED]); }
     if (opt_set("ABPOA_HIP_WIDE_COUNTERS")) {
-        // (slot 0: all-chunk body rows in bits 0-31, rows of 9-11 chunks among them in bits 32-47 (int32) / 48-62 (int16): rows_fast.h WCOUNT_BODY)
-        double body = 0, xl32 = 0, xl16 = 0; for (const AlnOut &o_ : ho) { body += (double)(o_.seg[0] & 0xffffffffll); xl32 += (double)((o_.seg[0] >> 32) & 0xffff);
-                xl16 += (double)(o_.seg[0] >> 48); }
+        double body = 0, xl32 = 0, xl16 = 0; for (const AlnOut &o_ : ho) { body += (double)wide_body_rows(o_.seg[WC_BODY]); xl32 += (double)wide_body_long32(o_.seg[WC_BODY]);
+                xl16 += (double)wide_body_long16(o_.seg[WC_BODY]); }
         fprintf(stderr,
             "[poa-device] round %d wide-loop rows per alignment (diagnostic build): all-chunk body %.0f | not eligible "
                     "(preds > 8 / distance) %.0f | ring-geometry %.0f | > 5 chunks %.0f | slow vectors straddle %.0f | key " "window / wrap %.0f | "
                     "9-11-chunk bodies int32 %.0f int16 %.0f\n", k,
-                    body / n_sets, sg[1] / n_sets, sg[2] / n_sets, sg[3] / n_sets, sg[4] / n_sets, sg[5] / n_sets, xl32 / n_sets, xl16 / n_sets); }
-    fprintf(stderr,
+                    body / n_sets, sg[WC_NOT_ELIGIBLE] / n_sets, sg[WC_RING_GEOMETRY] / n_sets, sg[WC_TOO_WIDE] / n_sets, sg[WC_STRADDLE] / n_sets, sg[WC_DECLINED] / n_sets,
+                    xl32 / n_sets, xl16 / n_sets); }
+    // the tails' counters (the two tails share the positions this line reads: RTAIL_* / DTAIL_*) -- only when the slots hold a tail layout
+    if (!row_slots && !(b.dbg & DBG_WALK_REPORT)) fprintf(stderr,
             "[poa-device] round %d tail means: steps %.0f  flag steps %.0f  slow steps %.0f  windows %.1f  window ticks %.0f (setup %.0f)  walk ticks %.0f\n",
-            k, st_ / n_sets, sg[2] / n_sets / 1000, sg[3] / n_sets / 1000, sg[4] / n_sets / 1000, sg[5] / n_sets, sg[0] / n_sets, sg[1] / n_sets);
+            k, st_ / n_sets, sg[RTAIL_FLAG_STEPS_K] / n_sets / 1000, sg[RTAIL_SLOW_STEPS_K] / n_sets / 1000, sg[RTAIL_WINDOWS_K] / n_sets / 1000, sg[RTAIL_WINDOW_TICKS] / n_sets,
+            sg[RTAIL_SETUP_TICKS] / n_sets, sg[RTAIL_WALK_TICKS] / n_sets);
 }
 
 // the device MSA of the first sets against the host routine on the host graph that was fed the same cigars

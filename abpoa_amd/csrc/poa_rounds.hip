@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(GT, 4) poa_rounds_kernel(const int slot, const
 #pragma unroll
     for (int w_ = GW - 1; w_ >= 0; --w_) if (sh_simd[w_] == sh_target) worker = w_;
     static_assert(GW == SPEC_WK, "one wavefront of the workgroup per walk of a backtrack");
-    const bool pair = !(b.dbg & 1024);               // (ABPOA_HIP_DBG bit 10: one wavefront per backtrack, for comparison)
+    const bool pair = !(b.dbg & DBG_ONE_WAVE_BACKTRACK);      // (one wavefront per backtrack, for comparison)
     for (int k = k_lo; k < n_reads; ++k) {
         const long long c0 = (long long)__builtin_amdgcn_s_memtime();
         if (tid == 0) sh_walk[8 * SPEC_WK] = 0;             // (no row of this round is complete; the barrier behind the prepare phase publishes it)

@@ -48,12 +48,12 @@ __host__ __device__ inline bool dir_for(int dir_mode, bool wide) { return ROUTE_
 
 __host__ __device__ __forceinline__ bool takes_fast(const DevBatch &b, const AlnDesc &d) {
     return fast_global_job(b.gap_mode, b.align_mode, b.wb, b.e1) && fast_global_aln(b.gap_mode, d.w, d.pad0) && (d.flags & ALN_FAST_OK) &&
-           ROUTE_FAST_LOOP_FITS(b.lds, d.qlen) && !(b.dbg & 64);
+           ROUTE_FAST_LOOP_FITS(b.lds, d.qlen) && !(b.dbg & DBG_NO_FAST_LOOPS);
 }
 // ... and among those, the ones whose rows are wide enough for the wide row loop (dp_wide_rows.hip); the rest take the narrow one
 __host__ __device__ __forceinline__ bool takes_wide(const DevBatch &b, const AlnDesc &d) { return takes_wide_band(b.lds, ROUTE_W(d.w, d.pad0)); }
 __host__ __device__ __forceinline__ bool takes_local(const DevBatch &b, const AlnDesc &d) {
-    return ROUTE_LOCAL_LOOP_JOB(b.gap_mode, b.align_mode, b.wb) && (d.flags & ALN_FAST_OK) && ROUTE_LOCAL_LOOP_FITS(b.lds, d.bits, d.qlen) && !(b.dbg & 64);
+    return ROUTE_LOCAL_LOOP_JOB(b.gap_mode, b.align_mode, b.wb) && (d.flags & ALN_FAST_OK) && ROUTE_LOCAL_LOOP_FITS(b.lds, d.bits, d.qlen) && !(b.dbg & DBG_NO_FAST_LOOPS);
 }
 // ... and which of the fast alignments write direction words instead of score records.
 // (Measured on MI355X: on 1 kb reads the words cost the row loop 5-8 % and save 36-42 % of the backtrack, a net 8-11 %; on 10 kb reads the all-chunks

@@ -94,41 +94,7 @@ __device__ __forceinline__ void slow_f_vectors(int vbase, int end_sn, int max_pr
     }
 }
 
-#ifdef ABPOA_HIP_PROFILE
-#define FSTAMP(I) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); long long t_ = (long long)__builtin_amdgcn_s_memtime(); fseg[I] += t_ - fseg_last; fseg_last = t_; }
-#else
-#define FSTAMP(I)
-#endif
-// Timing-only ablation switches (tools/kernel_bench.py with ABPOA_HIP_DBG=bits on the "prof" build): results are wrong on purpose.
-// Diagnostic builds (-DABPOA_HIP_WIDE_COUNTERS, with ABPOA_HIP_DBG=128 so that the tail keeps them): rows per path of the wide loop in AlnOut.seg --
-// 0 wide body, 1 not eligible (predecessor count / distance), 2 ring / geometry, 3 wider than the body's chunks, 4 slow vectors span two wavefronts, 5 wrap guard
-// -DABPOA_HIP_ROW_CENSUS (same hand-over): rows and clock ticks per body of the NARROW loop -- seg[i] = rows << 40 | ticks for i = 0 one predecessor
-// (tight loop), 1 two predecessors (tight loop), 2 three / four predecessors (straight-line body), 3 the exact bodies (fast / general); 4 = tile switches
-#ifdef ABPOA_HIP_ASM_CENSUS      // (-DABPOA_HIP_ROW_CENSUS -DABPOA_HIP_ASM_CENSUS: the census WITH the assembly loop -- slot 0 = its rows, slot 1 = the C++ copies of the one- / two-predecessor body)
-#define CENSUS_SLOT(I) ((I) == 0 ? 1 : (I))
-#else
-#define CENSUS_SLOT(I) (I)
-#endif
-#ifdef ABPOA_HIP_ROW_CENSUS
-#define CENSUS_T0() const long long cen_t0 = (long long)__builtin_amdgcn_s_memtime();
-#define CENSUS(I) { fseg[CENSUS_SLOT(I)] += (1ll << 40) + ((long long)__builtin_amdgcn_s_memtime() - cen_t0); }
-#else
-#define CENSUS_T0()
-#define CENSUS(I)
-#endif
-#ifdef ABPOA_HIP_WIDE_COUNTERS
-#define WCOUNT(I) { fseg[I] += 1; }
-// (single-wave wide bodies) slot 0 counts the row in its low 32 bits, a row of 9-11 chunks (the long-read form) also in bits 32-47 (int32) / 48-62 (int16)
-#define WCOUNT_BODY(NCH) { fseg[0] += 1 + ((NCH) >= 9 ? (I16 ? 1ll << 48 : 1ll << 32) : 0); }
-#else
-#define WCOUNT(I) {}
-#define WCOUNT_BODY(NCH) {}
-#endif
-#ifdef ABPOA_HIP_ABLATE
-#define ABL(BIT) (b.dbg & (BIT))
-#else
-#define ABL(BIT) false
-#endif
+// (FSTAMP, CENSUS, WCOUNT, ABL and the slots they take: the diagnostic builds, diag.h)
 template <typename T, int GAP, bool WIDEB = false, bool DIR = false, bool XL = false>
 __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, const FastIO<T> &io, const uint8_t *s_query,
                                           long long &cursor_out, long long &n_cells_out, int &status, int &rows_done_out, int &last_done, long long *fseg, int *best_out = nullptr) {
@@ -208,7 +174,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
     // first row that reaches the maximum, in the reference's own row order) and, with z-drop, the test that ends the row loop
     const bool extend = sgpr(b.align_mode == ABPOA_HIP_EXTEND_MODE ? 1 : 0) != 0;
     int ex_best = inf, ex_i = 0, ex_j = 0, ex_rem = 0; bool zstop = false;
-    const bool asm_tight_on = sgpr(!(b.dbg & 2048) && RC == 128 && b.align_mode != ABPOA_HIP_EXTEND_MODE ? 1 : 0) != 0;      // (rows_tight_asm.h; read once: the argument record lives in constant memory)
+    const bool asm_tight_on = sgpr(!(b.dbg & DBG_CXX_TIGHT_LOOP) && RC == 128 && b.align_mode != ABPOA_HIP_EXTEND_MODE ? 1 : 0) != 0;      // (rows_tight_asm.h; read once: the argument record lives in constant memory)
     int cur = 0, n_vec_lane = 0;                    // arena cursor in units of PN cells (one reference SIMD vector); cell count: per-lane sums of the flushed rows' vectors
     const int cap_pn = (int)(d.plane_cap / PN > 0x7fffffffLL ? 0x7fffffffLL : d.plane_cap / PN);
     const int cap_turbo = cap_pn - (DIR ? dir_units(NV) + NV * CWR : NV * CW);       // arena room test of the straight-line rows (at most NV vectors)
@@ -386,9 +352,9 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 }
             }
             const int Hout = hl;
-            if (!ABL(1)) { if (I16) *(int *)(H + (long long)rel * CW) = Hout & 0xffff; else { int2 rec; rec.x = Hout; rec.y = 0; *(int2 *)(H + (long long)rel * CW) = rec; } }      // ({H, flag 0 = not known}; lanes past the band write cells the next row overwrites)
-            if (to_ring && !ABL(2)) { int *qd = fr + my_slot + 2 + rel; qd[0] = in_band ? (I16 ? (int)(((unsigned)Hout & 0xffffu) | ((unsigned)inf << 16)) : Hout) : infw; }
-            if (!ABL(4)) {
+            if (!ABL(ABL_NO_ARENA_STORE)) { if (I16) *(int *)(H + (long long)rel * CW) = Hout & 0xffff; else { int2 rec; rec.x = Hout; rec.y = 0; *(int2 *)(H + (long long)rel * CW) = rec; } }      // ({H, flag 0 = not known}; lanes past the band write cells the next row overwrites)
+            if (to_ring && !ABL(ABL_FAST_NO_RING_STORE)) { int *qd = fr + my_slot + 2 + rel; qd[0] = in_band ? (I16 ? (int)(((unsigned)Hout & 0xffffu) | ((unsigned)inf << 16)) : Hout) : infw; }
+            if (!ABL(ABL_FAST_NO_ARGMAX)) {
                 const bool is_end = (v == end_sn);
                 int cand = Hout;
                 if (end_sn == qlen_sn) cand = (is_end && col > qlen) ? inf : cand;
@@ -407,7 +373,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         if (nfast < 0) nfast = 0;
         if (nfast > 0 && __any(vvl < nfast && h < fast_lo)) nfast = 0;
         int F1 = inf, F2 = inf;
-        if (nfast > 0 && !ABL(8)) {
+        if (nfast > 0 && !ABL(ABL_FAST_NO_F_CLOSED_FORM)) {
             const int g1 = hs + le1;
             const int S1 = wave_scan_max_i32(wave_shr1(first - e1, g1));
             F1 = imax(S1 - cf1, inj1);
@@ -415,12 +381,12 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                             if (nfast < nvec || c + 1 < nch) { const int lastl = nfast * PN - 1; first2 = __builtin_amdgcn_readlane(imax(S2, g2), lastl) - lastl * e2; } }
             if (nfast < nvec || c + 1 < nch) { const int lastl = nfast * PN - 1; first = __builtin_amdgcn_readlane(imax(S1, g1), lastl) - lastl * e1; }
         }
-        if (nfast < nvec && !ABL(32)) {
+        if (nfast < nvec && !ABL(ABL_FAST_NO_SLOW_F)) {
             T f1t = (T)F1, f2t = (T)F2, fi = (T)first, fi2 = (T)first2;
             slow_f_vectors<T, GAP>(vb, end_sn, max_pe, nfast, l, vvl, (T)hs, (T)inf, (T)e1, (T)oe1, (T)o1, (T)e2, (T)oe2, (T)o2, f1t, f2t, fi, fi2);
             F1 = (int)f1t; F2 = (int)f2t; first = (int)fi; first2 = (int)fi2;
         }
-        FSTAMP(2)
+        FSTAMP(PROF_FCHAIN)
         int Hout, E1out, E2out = inf;
         if (GAP == 1) {
             const int tmp = imax(h, E1v);
@@ -459,7 +425,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             ct_pH = __builtin_amdgcn_readlane(Hout, 63); ct_pF1 = __builtin_amdgcn_readlane(F1, 63); if (GAP == 2) ct_pF2 = __builtin_amdgcn_readlane(F2, 63);
         }
         // (DIR: only a row that keeps its records stores them, and only its in-band lanes do: the row's words start right behind its last record)
-        if (ABL(1) || (DIR && !(row_spill && in_band))) {}
+        if (ABL(ABL_NO_ARENA_STORE) || (DIR && !(row_spill && in_band))) {}
         else if (CSP) {      // compact records (CWR): what a far successor and the global best read
             if (I16 && GAP == 1) *(int *)(Hrec + (long long)rel * CWR) = he;
             else if (I16) { int2 rec; rec.x = he; rec.y = E2out & 0xffff; *(int2 *)(Hrec + (long long)rel * CWR) = rec; }
@@ -471,13 +437,13 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         else if (GAP == 1) { int4 rec; rec.x = Hout; rec.y = E1out; rec.z = F1; rec.w = mflag; *(int4 *)(Hrec + (long long)rel * CW) = rec; }
         else { int4 r0, r1; r0.x = Hout; r0.y = E1out; r0.z = E2out; r0.w = F1; r1.x = F2; r1.y = mflag; r1.z = 0; r1.w = 0; int4 *dst = (int4 *)(Hrec + (long long)rel * CW); dst[0] = r0;
                 dst[1] = r1; }
-        if (to_ring && !ABL(2)) {
+        if (to_ring && !ABL(ABL_FAST_NO_RING_STORE)) {
             int *qd = fr + my_slot + 2 + rel;
             if (I16) { qd[0] = in_band ? he : infw; if (GAP == 2) qd[RCS] = in_band ? E2out : inf; }
             else if (EPACK) { qd[0] = in_band ? Hout : inf; qd[RCS] = in_band ? (int)((unsigned)(Hout - E1out) | ((unsigned)(Hout - E2out) << 16)) : 0; }
             else { qd[0] = in_band ? Hout : inf; qd[RCS] = in_band ? E1out : inf; if (GAP == 2) qd[2 * RCS] = in_band ? E2out : inf; }
         }
-        if (!ABL(4)) {   // running arg-max candidate of this lane, reference :1043-1057
+        if (!ABL(ABL_FAST_NO_ARGMAX)) {   // running arg-max candidate of this lane, reference :1043-1057
             const bool is_end = (v == end_sn);
             int cand = Hout;
             if (end_sn == qlen_sn) cand = (is_end && col > qlen) ? inf : cand;
@@ -488,7 +454,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         }
     };
     auto pad_ring = [&](int nch, int my_slot) __attribute__((always_inline)) {        // "inf" after the band, up to the ring width
-        if (!ABL(2)) for (int c = nch; c < (RC >> 6); ++c) {
+        if (!ABL(ABL_FAST_NO_RING_STORE)) for (int c = nch; c < (RC >> 6); ++c) {
             int *qd = fr + my_slot + 2 + c * 64 + lane;
             qd[0] = infw; if (NPW > 1) qd[RCS] = EPACK ? 0 : inf; if (NPW > 2) qd[2 * RCS] = inf;
         }
@@ -871,10 +837,10 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         set_band(std::true_type{}, mn_mi, mx_mi, min_pb);
         const int nvr = end_sn - beg_sn + 1, Wr = nvr * PN, nch = (Wr + 63) >> 6;
         bool ok = nch <= NCHX && Wr <= RC && max_pe >= beg_sn;
-        if (!ok) { WCOUNT(nch > NCHX ? 3 : 2); return 0; }
+        if (!ok) { WCOUNT(nch > NCHX ? WC_TOO_WIDE : WC_RING_GEOMETRY); return 0; }
         // vectors beyond every predecessor's band (literal masked scan) must all sit in the row's last chunk
         if (end_sn > max_pe) ok = ok && ((max_pe + 1 - beg_sn) / NV == nch - 1);
-        if (!ok) { WCOUNT(4); return 0; }
+        if (!ok) { WCOUNT(WC_STRADDLE); return 0; }
         if (cur + row_units(nvr, row_spill) > cap_pn) return -2;
         return nch;
     };
@@ -887,7 +853,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
 #pragma unroll
             for (int c = 0; c < NCHX; ++c) { const int col = colb + 64 * c; qoffx[c] = (col >= 1 && col <= qlen) ? qat(col - 1) : m; }
         }
-        FSTAMP(0)
+        FSTAMP(PROF_HDR)
         const int *mrow = s_mx + base * m1;
         int q[NCH], Mv[NCH], E1v[NCH], E2v[NCH], kb[NCH];
         int kE1[NCH], kE2[NCH];                                     // (DIR) 1 + list index of the first predecessor holding the maximum E1 / E2 of the column
@@ -973,7 +939,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 }
             }
         }
-        FSTAMP(1)
+        FSTAMP(PROF_GATHER)
         // ---- H before F, wrap guard of the closed form (lanes of vectors <= max_pre_end_sn, as chunk_tail)
         //      (checked over ALL lanes: lanes outside the closed-form vectors hold inf + q, which is above the limit unless the penalties are
         //       extreme -- then the row simply takes the exact bodies)
@@ -1027,7 +993,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             step(std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xC>{});
         }
         const unsigned kbst = (unsigned)__builtin_amdgcn_readlane((int)amk, 63);
-        FSTAMP(2)
+        FSTAMP(PROF_FCHAIN)
         // ---- carry chain over the chunk totals, then F of every chunk.  seed[c] = "first - e" of chunk c; seed[c + 1] = max(total[c], seed[c]) - 64 e.
         //      (the chain runs in the vector unit on wave-uniform values -- the totals are read out of lane 63 back to back and the
         //       dependent max / subtract steps need no trip through the scalar unit)
@@ -1040,7 +1006,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             if (GAP == 2) seed2[c + 1] = carry_next(__builtin_amdgcn_readlane(imax(s2[c], g2[c]), 63), seed2[c], e2); else seed2[c + 1] = INT_MIN;
         }
         if (!I16) { if (__builtin_expect(argmax_declines32(kbst), 0)) return 0; }
-        FSTAMP(3)
+        FSTAMP(PROF_STORE)
         // ---- from here on the row is committed
         T *const Hrow = io.planes + (long long)cur * PN + (long long)lane * CWR;
         off_pn = cur + ((DIR && row_spill) ? (end_sn - beg_sn + 1) * CWR : 0); cur += row_units(end_sn - beg_sn + 1, row_spill);
@@ -1129,7 +1095,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         }
         // "inf" up to the ring width
         for (int c = NCH; c < (RC >> 6); ++c) { qd[c * 64] = infw; if (NPW > 1) qd[RCS + c * 64] = EPACK ? 0 : inf; if (NPW > 2) qd[2 * RCS + c * 64] = inf; }
-        FSTAMP(4)
+        FSTAMP(PROF_ARGMAX)
         // ---- row arg-max
         mi = -1;
         if (I16) { rowmax = argmax_value16(kbst); if (rowmax > inf) mi = argmax_index16(kbst, PN, qlen); }
@@ -1156,7 +1122,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         set_band(std::true_type{}, mn_mi, mx_mi, min_pb);
         const int Wr = (end_sn - beg_sn + 1) * PN;
         if (!(allring & GEO_RING) || Wr > RC) return 0;
-        FSTAMP(0)
+        FSTAMP(PROF_HDR)
         if (!reserve()) return 2;
         to_ring = true;
         T *H = io.planes + (long long)off_pn * PN;
@@ -1171,10 +1137,10 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             if (c >= 2) qc = (col >= 1 && col <= qlen) ? qat(col - 1) : m;
             const int q = mrow[qc];
             int Mv = lane, E1v = inf, E2v = inf, kb = 0, kE1 = 1, kE2 = 1;
-            if (!ABL(16)) from_ring(0, pr[0], pgeo[0], col, Mv, E1v, E2v, kb, 1, kE1, kE2, q);
-            if (NPC >= 2 && !ABL(16)) from_ring(1, pr[1], pgeo[1], col, Mv, E1v, E2v, kb, 2, kE1, kE2, q);
+            if (!ABL(ABL_FAST_NO_GATHER)) from_ring(0, pr[0], pgeo[0], col, Mv, E1v, E2v, kb, 1, kE1, kE2, q);
+            if (NPC >= 2 && !ABL(ABL_FAST_NO_GATHER)) from_ring(1, pr[1], pgeo[1], col, Mv, E1v, E2v, kb, 2, kE1, kE2, q);
             if (NPC >= 4) { if (np > 2) from_ring(2, pr[2], pgeo[2], col, Mv, E1v, E2v, kb, 3, kE1, kE2, q); if (np > 3) from_ring(3, pr[3], pgeo[3], col, Mv, E1v, E2v, kb, 4, kE1, kE2, q); }
-            FSTAMP(1)
+            FSTAMP(PROF_GATHER)
             chunk_tail(c, nch, Wr, Mv, E1v, E2v, q, kb, first, first2, H, my_slot, kE1, kE2);
         }
         pad_ring(nch, my_slot);
@@ -1262,7 +1228,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
         }
         switch_tile(t0);
 #ifdef ABPOA_HIP_ROW_CENSUS
-        { asm volatile("" :: "v"(tv_meta), "v"(tv_p0), "v"(tv_tb), "v"(tv_rterm)); fseg[4] += (1ll << 40) + ((long long)__builtin_amdgcn_s_memtime() - cen_ts); }
+        { asm volatile("" :: "v"(tv_meta), "v"(tv_p0), "v"(tv_tb), "v"(tv_rterm)); fseg[CEN_TILE] += census_pack(1, (long long)__builtin_amdgcn_s_memtime() - cen_ts); }
 #endif
         const int r_hi = imin(t0 + 64, gn - 1);
         auto commit_row = [&](int ti, bool ring) __attribute__((always_inline)) {   // v_writelane x3 (no clang builtin); M0 = lane select (two different SGPRs would break the constant-bus limit)
@@ -1294,13 +1260,13 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                     rterm = __builtin_amdgcn_readlane(tv_rterm, ti_); base = meta_ & 0xff; np = (meta_ >> 8) & 0xff;
                     const int nch_ = ilp_band(row, ti_);
                     if (nch_ == -2) { status = ABPOA_HIP_STATUS_OVERFLOW; break; }
-                    if (nch_ == 2 && ilp_chunks(std::integral_constant<int, 2>{}, nch_, row, ti_) == 1) { commit_row(ti_, true); CENSUS(3) ++row; continue; }
+                    if (nch_ == 2 && ilp_chunks(std::integral_constant<int, 2>{}, nch_, row, ti_) == 1) { commit_row(ti_, true); CENSUS(CEN_EXACT) ++row; continue; }
                 }
                 two_chunk_streak = 0;
             }
             // the tight loop in hand-placed assembly (rows_tight_asm.h): int16, affine, direction words -- the 1 kb production job.  It stops in front of the first
             // row it does not take and says why; that row goes through the bodies below, then the loop is entered again.  (Not in the diagnostic builds, whose
-            // ablation bits / clocks / censuses live in the C++ bodies; ABPOA_HIP_DBG bit 11 keeps the compiler's loop, for comparison.)
+            // ablation bits / clocks / censuses live in the C++ bodies; DBG_CXX_TIGHT_LOOP keeps the compiler's loop, for comparison.)
             bool cxx_tight = true;
 #if !defined(ABPOA_HIP_ABLATE) && !defined(ABPOA_HIP_PROFILE) && (!defined(ABPOA_HIP_ROW_CENSUS) || defined(ABPOA_HIP_ASM_CENSUS)) && !defined(ABPOA_HIP_NO_ASM_TIGHT)
             if constexpr (!WIDEB && I16 && GAP == 1 && DIR) {
@@ -1326,7 +1292,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                     ok_ = code == 1 ? 0 : (code == 2 ? -1 : 1);
                     cxx_tight = false;
 #ifdef ABPOA_HIP_ASM_CENSUS
-                    fseg[0] += ((long long)(row - asm_row0) << 40) + ((long long)__builtin_amdgcn_s_memtime() - asm_t0);
+                    fseg[CEN_ASM_LOOP] += census_pack(row - asm_row0, (long long)__builtin_amdgcn_s_memtime() - asm_t0);
 #endif
                 }
             }
@@ -1342,7 +1308,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 ok_ = np == 1 ? turbo_body(std::integral_constant<int, 1>{}, std::false_type{}, row, ti_) : turbo_body(std::integral_constant<int, 2>{}, std::false_type{}, row, ti_);
                 if (__builtin_expect(ok_ != 1, 0)) break;
                 commit_row(ti_, true);
-                CENSUS(np == 1 ? 0 : 1)
+                CENSUS(np == 1 ? CEN_ONE_PRED : CEN_TWO_PRED)
                 if (++row >= r_hi || zstop) break;
             }
             last_done = row - 1;
@@ -1355,22 +1321,22 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
             base = meta & 0xff; np = (meta >> 8) & 0xff;
             if constexpr (DIR) row_spill = (meta >> 21) & 1;
             if (!WIDEB && ((meta >> 18) & 1)) {                       // three or four predecessors: the straight-line body, outside the tight loop
-                if (turbo_body(std::integral_constant<int, 4>{}, std::true_type{}, row, ti) == 1) { commit_row(ti, true); CENSUS(2) ++row; continue; }
+                if (turbo_body(std::integral_constant<int, 4>{}, std::true_type{}, row, ti) == 1) { commit_row(ti, true); CENSUS(CEN_MANY_PRED) ++row; continue; }
             }
             if (!WIDEB && ((meta >> 20) & 1)) {                       // five to eight predecessors
-                if (turbo_body(std::integral_constant<int, 8>{}, std::true_type{}, row, ti) == 1) { commit_row(ti, true); CENSUS(2) ++row; continue; }
+                if (turbo_body(std::integral_constant<int, 8>{}, std::true_type{}, row, ti) == 1) { commit_row(ti, true); CENSUS(CEN_MANY_PRED) ++row; continue; }
             }
             // one or two predecessors and the tight loop declined: most often the row's band reaches one
             if (!WIDEB && (((meta >> 17) & 1) ? ok_ == 0 : (DIR && ((meta >> 22) & 1)))) {
                                                                       // vector beyond its predecessors' (every PN-th row of a chain) -- the copies that take those vectors
                 const int ok3 = np == 1 ? turbo_body(std::integral_constant<int, 1>{}, std::true_type{}, row, ti) : turbo_body(std::integral_constant<int, 2>{}, std::true_type{}, row, ti);
-                if (ok3 == 1) { commit_row(ti, true); CENSUS(np == 1 ? 0 : 1) ++row; continue; }
+                if (ok3 == 1) { commit_row(ti, true); CENSUS(np == 1 ? CEN_ONE_PRED : CEN_TWO_PRED) ++row; continue; }
             }
             if (GAP != 0 && !WIDEB && ((meta >> 19) & 1)) {           // narrow kernel, the straight-line bodies declined (a band of 65-128 columns for a stretch of
                                                                       // rows, a predecessor beyond the score ring, ...): the all-chunks body with two chunks
                 const int nch_ = ilp_band(row, ti);
                 if (nch_ == -2) { status = ABPOA_HIP_STATUS_OVERFLOW; break; }
-                if (nch_ >= 1 && nch_ <= 2 && ilp_chunks(std::integral_constant<int, 2>{}, nch_, row, ti) == 1) { two_chunk_streak = nch_ == 2; commit_row(ti, true); CENSUS(3) ++row; continue; }
+                if (nch_ >= 1 && nch_ <= 2 && ilp_chunks(std::integral_constant<int, 2>{}, nch_, row, ti) == 1) { two_chunk_streak = nch_ == 2; commit_row(ti, true); CENSUS(CEN_EXACT) ++row; continue; }
             }
             if (WIDEB && ((meta >> 19) & 1)) {                        // wide band: every chunk of the row at once
                 const int nch_ = ilp_band(row, ti);
@@ -1390,10 +1356,10 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                         else ok2 = ilp_chunks(std::integral_constant<int, 11>{}, nch_, row, ti);
                     }
                     else ok2 = 0;
-                    if (ok2 == 1) { WCOUNT_BODY(nch_); commit_row(ti, true); FSTAMP(5) ++row; continue; }
-                    WCOUNT(5);
+                    if (ok2 == 1) { WCOUNT_BODY(nch_); commit_row(ti, true); FSTAMP(PROF_TOP) ++row; continue; }
+                    WCOUNT(WC_DECLINED);
                 }
-            } else if (WIDEB) WCOUNT(1);
+            } else if (WIDEB) WCOUNT(WC_NOT_ELIGIBLE);
             am_key = 0; am_val = INT_MIN; am_v = 0; am_isend = 0; am_any = false;
             int rc = 0;
             {
@@ -1404,7 +1370,7 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 }
                 if (rc == 0) rc = general_body(row, ti);
                 if (rc == 2) { status = ABPOA_HIP_STATUS_OVERFLOW; break; }
-                FSTAMP(3)
+                FSTAMP(PROF_STORE)
                 // ---- row arg-max (tie-break: lowest lane residue, then the end_sn vector, then the lowest vector), reference :1043-1057
                 mi = -1;
                 if (I16) {
@@ -1422,10 +1388,10 @@ __device__ __forceinline__ void rows_fast(const DevBatch &b, const AlnDesc &d, c
                 }
             }
             commit_row(ti, to_ring);
-            FSTAMP(4)
-            CENSUS(3)
+            FSTAMP(PROF_ARGMAX)
+            CENSUS(CEN_EXACT)
 #ifdef ABPOA_HIP_ROW_CENSUS
-            fseg[5] += np > 4 ? (1ll << 40) : (((meta >> 16) & 1) ? (1ll << 20) : 1ll);      // why the exact bodies: > 4 predecessors | straight-line body declined | a predecessor beyond the ring
+            fseg[CEN_WHY] += np > 4 ? census_why_pack(1, 0, 0) : (((meta >> 16) & 1) ? census_why_pack(0, 1, 0) : census_why_pack(0, 0, 1));      // why the exact bodies
 #endif
             ++row;
         }
@@ -1479,15 +1445,15 @@ __device__ __forceinline__ void align_fast_rows(const DevBatch &b, const AlnDesc
     WG_SYNC();
     long long cursor = 0, n_cells = 0; int status = 0, rows_done = 0, last_done = 0;
     const long long clk0 = (long long)__builtin_amdgcn_s_memtime();
-    long long fseg[6] = {0, 0, 0, 0, 0, 0};
+    long long fseg[DIAG_SLOTS] = {0, 0, 0, 0, 0, 0};
     int best3[3] = {d.inf_min, 0, 0};
     rows_fast<T, GAP, WIDEB, DIR, XL>(b, d, io, s_query, cursor, n_cells, status, rows_done, last_done, fseg, best3);
     const long long clk1 = (long long)__builtin_amdgcn_s_memtime();
 #if !defined(ABPOA_HIP_WIDE_COUNTERS) && !defined(ABPOA_HIP_ROW_CENSUS)
-    fseg[5] = (long long)__builtin_amdgcn_s_getreg(63492) | ((long long)__builtin_amdgcn_s_getreg(6164) << 32);      // HW_ID | XCC_ID << 32: where the wave ran (ABPOA_HIP_IMBAL placement report)
+    fseg[PLACE_KEY] = placement_pack((long long)__builtin_amdgcn_s_getreg(GETREG_HW_ID), (long long)__builtin_amdgcn_s_getreg(GETREG_XCC_ID));      // where the wave ran (ABPOA_HIP_IMBAL placement report)
 #endif
     if (lane == 0) { GLOBAL_AS AlnOut *o = vgpr_ptr(out_rec); o->status = status; o->n_cells = n_cells; o->cells_used = cursor; o->clk_dp = clk1 - clk0;
-            o->n_rows_done = rows_done; for (int i_ = 0; i_ < 6; ++i_) o->seg[i_] = fseg[i_];
+            o->n_rows_done = rows_done; for (int i_ = 0; i_ < DIAG_SLOTS; ++i_) o->seg[i_] = fseg[i_];
             if (b.align_mode == ABPOA_HIP_EXTEND_MODE) { o->best_score = best3[0]; o->best_row = best3[1]; o->best_col = best3[2]; } }
     // every way out of the row loop ends the progress word: rows up to last_done are complete, or -1 after a status (backtrack_dir.h SPEC_PROG_*)
     if (io.prog_a >= 0) {

@@ -92,7 +92,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
         int nfast = local ? nvec : imin(nvec, max_pre_ - vb + 1);
         if (nfast < 0) nfast = 0;
         if (nfast > 0 && ((int)first < fast_lo || __any(vvl < nfast && (int)h < fast_lo))) nfast = 0;
-        if (b.dbg & 4) nfast = 0;
+        if (ABL(ABL_GEN_LITERAL_F_SCAN)) nfast = 0;
         if (nfast > 0) {
             int g = (int)h + le1;
             g = lane == 0 ? imax(g, (int)first) : g;
@@ -123,7 +123,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
     int last_done = 0;                                        // last row the loop reached (z-drop may stop early)
     long long clk0 = 0, clk1 = 0;
 #ifdef ABPOA_HIP_PROFILE
-    long long seg_keep[6] = {0, 0, 0, 0, 0, 0};
+    long long seg_keep[DIAG_SLOTS] = {0, 0, 0, 0, 0, 0};
 #endif
     {
     // ------------------------------------------------------------------ row 0, reference :553-662
@@ -191,14 +191,11 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
     __syncthreads();
 
 #ifdef ABPOA_HIP_PROFILE
-    long long seg[6] = {0, 0, 0, 0, 0, 0}, seg_last = 0;
-#define STAMP(I) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); long long t_ = (long long)__builtin_amdgcn_s_memtime(); seg[I] += t_ - seg_last; seg_last = t_; }
-#else
-#define STAMP(I)
+    long long fseg[DIAG_SLOTS] = {0, 0, 0, 0, 0, 0}, fseg_last = 0;      // (FSTAMP: diag.h)
 #endif
     clk0 = (long long)__builtin_amdgcn_s_memtime();
 #ifdef ABPOA_HIP_PROFILE
-    seg_last = clk0;
+    fseg_last = clk0;
 #endif
     const int remain_end = (banded || b.zdrop > 0) ? row_remain[gn - 1] : 0;
     const bool need_max = local || extend || banded;
@@ -284,7 +281,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
             }
             lr_blk += RLH;
         }
-        STAMP(5)
+        FSTAMP(PROF_TOP)
         last_done = row;
         const int ti = row - tile_beg;
         // ====================================================================================================
@@ -292,7 +289,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
         // rows are still in the score ring, band <= 128 columns, successors inside the left/right window.  Straight-line:
         // one record read, two geometry reads, one batch of score reads per chunk, one reduction.  Same arithmetic as the
         // general row below (which handles everything else), so the results are identical.
-        if (GAP != 0 && banded && !local && !extend && !(b.dbg & 64)) {
+        if (GAP != 0 && banded && !local && !extend && !(b.dbg & DBG_NO_FAST_LOOPS)) {
             const int4 fr = uniform4(S.t_fast[ti]);
             if (fr.x < 0) {
                 const int2 lr = uniform2(S.l_lr[row % RL]);
@@ -320,7 +317,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
                     const int bs0 = imax(g0.x, fbeg_sn), bs1 = imax(g1.x, fbeg_sn);
                     const int esh0 = imin(imin(g0.y + 1, fend_sn), dp_sn - 1), esh1 = imin(imin(g1.y + 1, fend_sn), dp_sn - 1);
                     const int ese0 = imin(g0.y, fend_sn), ese1 = imin(g1.y, fend_sn);
-                    T first = 0, first2 = 0; int dbgv = 0;
+                    T first = 0, first2 = 0;
                     int am_val = INT_MIN, am_v = 0, am_isend = 0; bool am_any = false; unsigned am_key = 0;
 #pragma unroll
                     for (int c = 0; c < 2; ++c) {
@@ -350,17 +347,14 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
                         int nfast = imin(nvec, fmax_pre - (fbeg_sn + c * NV) + 1);
                         if (nfast < 0) nfast = 0;
                         if (nfast > 0 && __any(vvl < nfast && (int)h < fast_lo)) nfast = 0;
-                        if (b.dbg & 4) nfast = 0;
+                        if (ABL(ABL_GEN_LITERAL_F_SCAN)) nfast = 0;
                         T F1 = inf, F2 = inf;
                         if (nfast > 0) {
                             int fi = (int)first;
-                            int dcv = 0;
-                            F1 = (T)fast_f_chain<T>((int)hs, fi, nfast, l, vvl, (int)oe1, (int)e1, (int)o1, cl1, inj1, &dcv);
-                            if (b.dbg & 512) F1 = (T)dcv;
+                            F1 = (T)fast_f_chain<T>((int)hs, fi, nfast, l, vvl, (int)oe1, (int)e1, (int)o1, cl1, inj1);
                             first = (T)fi;
                             if (GAP == 2) { int fi2 = (int)first2; F2 = (T)fast_f_chain<T>((int)hs, fi2, nfast, l, vvl, (int)oe2, (int)e2, (int)o2, cl2, inj2); first2 = (T)fi2; }
                         }
-                        if ((b.dbg & 256) && c == 0) dbgv = ((int)first & 0xffff) | (nfast << 16) | (nvec << 20) | ((__builtin_amdgcn_readlane((int)hs, 15) & 0xff) << 24);
                         if (nfast < nvec) slow_f_tail(c, fbeg_sn, fend_sn, fmax_pre, nfast, hs, F1, F2, first, first2);
                         T Hout, E1out, E2out = 0;
                         if (GAP == 1) {                                          // reference :876-883
@@ -390,7 +384,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
                     if (lane == 0) S.b_rec[row % RB].w = row;
                     int mi = -1;
                     if (sizeof(T) == 2) {
-                        const unsigned kb = (b.dbg & 128) ? wave_max_u32(am_key) : wave_max_u32_b(am_key);
+                        const unsigned kb = wave_max_u32_b(am_key);
                         const int vmax = (int)(kb >> 16) - 32768;
                         if (vmax > d.inf_min) { mi = (2047 - (int)(kb & 0x7ff)) * PN + (PN - 1 - (int)((kb >> 12) & 0xf)); if (mi > qlen) mi = -1; }
                     } else {
@@ -403,7 +397,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
                             if (mi > qlen) mi = -1;
                         }
                     }
-                    if (b.want_trace && lane == 0) row_max_i[row] = (b.dbg & 256) ? dbgv : mi;
+                    if (b.want_trace && lane == 0) row_max_i[row] = mi;
                     {                                                            // reference :1059-1067
                         const int out_i = mi + 1;
                         int2 a2 = S.l_lr[(so0 >= 0 ? so0 : 0) % RL], b2 = S.l_lr[(so1 >= 0 ? so1 : 0) % RL];
@@ -465,7 +459,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
         T *H = planes + off;
         const int my_slot = row % ring_rows;
         T *my_ring = s_ring + (long long)my_slot * NPR * ring_cols;
-        const int nchunk = (b.dbg & 8) ? 0 : (Wr + 63) >> 6;
+        const int nchunk = ABL(ABL_GEN_NO_CHUNKS) ? 0 : (Wr + 63) >> 6;
         T first = 0, first2 = 0;
         // running arg-max state of this lane (reference :1043-1057)
         int am_val = INT_MIN, am_v = 0, am_isend = 0; bool am_any = false;
@@ -480,7 +474,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
             for (int c2 = 0; c2 < 2; ++c2) { const int cc = beg_sn * PN + c2 * 64 + lane; qc_cache[c2] = (cc >= 1 && cc <= qlen) ? (int)s_query[cc - 1] : -1; }
         }
 
-        STAMP(0)
+        FSTAMP(PROF_HDR)
         for (int c = 0; c < nchunk; ++c) {
             const int rel = c * 64 + lane;
             const bool in_band = rel < Wr;
@@ -489,7 +483,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
             T Mv = inf, E1v = inf, E2v = inf;
             // query profile value, reference :504-510
             T q = 0;
-            if (!(b.dbg & 32)) {
+            if (!ABL(ABL_GEN_NO_QUERY_PROFILE)) {
                 int qc;
                 if (q_in_lds) qc = c == 0 ? qc_cache[0] : c == 1 ? qc_cache[1] : ((col >= 1 && col <= qlen) ? (int)s_query[col - 1] : -1);
                 else qc = (in_band && col >= 1 && col <= qlen) ? gld_u8(g_query + col - 1) : -1;
@@ -497,7 +491,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
                 q = (in_band && qc >= 0) ? (T)qv : (T)0;
             }
             // ---- predecessors, reference :722-761 / :803-852 / :912-969
-            if (b.dbg & 16) { Mv = (T)(col & 15); E1v = inf; }
+            if (ABL(ABL_GEN_FAKE_GATHER)) { Mv = (T)(col & 15); E1v = inf; }
             else if (all_ring) {
                 auto gather_ring = [&](auto npc) __attribute__((always_inline)) {
                     constexpr int N = decltype(npc)::value;
@@ -582,7 +576,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
                 if (in_ring) gather(std::true_type{}, s_ring + (long long)pslot * NPR * ring_cols, (long long)ring_cols);
                 else gather(std::false_type{}, planes + poff, (long long)Wp);       // HBM copy (older or over-wide row)
             }
-            STAMP(1)
+            FSTAMP(PROF_GATHER)
             // ---- in-row part
             T Hout, E1out = 0, E2out = 0, F1 = inf, F2 = inf;
             if (GAP == 0) {
@@ -599,7 +593,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
                 int nfast = local ? nvec : imin(nvec, max_pre_end_sn - (beg_sn + c * NV) + 1);
                 if (nfast < 0) nfast = 0;
                 if (nfast > 0 && __any(vvl < nfast && (int)h < fast_lo)) nfast = 0;
-                if (b.dbg & 4) nfast = 0;
+                if (ABL(ABL_GEN_LITERAL_F_SCAN)) nfast = 0;
                 if (nfast > 0) {
                     int fi = (int)first;
                     F1 = (T)fast_f_chain<T>((int)hs, fi, nfast, l, vvl, (int)oe1, (int)e1, (int)o1, cl1, inj1);
@@ -627,8 +621,8 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
                     Hout = hh;
                 }
             }
-            STAMP(2)
-            if (in_band && !(b.dbg & 1)) {
+            FSTAMP(PROF_FCHAIN)
+            if (in_band && !ABL(ABL_NO_ARENA_STORE)) {
                 H[rel] = Hout;
                 if (GAP != 0) {
                     H[(long long)PL_E1 * Wr + rel] = E1out;
@@ -653,13 +647,13 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
                     } else if (!am_any || (is_end ? cand >= am_val : cand > am_val)) { am_val = cand; am_v = v; am_isend = is_end; am_any = true; }
                 }
             }
-            STAMP(3)
+            FSTAMP(PROF_STORE)
         }
         if (to_ring && lane == 0) S.b_rec[row % RB].w = row;      // H/E of this row are now readable from the score ring
         // ---- row arg-max, reference simd_abpoa_max_in_row :1043-1057 (tie-break: lowest lane, then the
         //      end_sn vector, then the lowest vector) and band hand-over :1059-1067
         int mx = d.inf_min, mi = -1;
-        if (need_max && (b.dbg & 2)) { mx = 0; mi = imin(qlen, row + 1); }
+        if (need_max && ABL(ABL_GEN_FAKE_ARGMAX)) { mx = 0; mi = imin(qlen, row + 1); }
         else if (need_max) {
             if (sizeof(T) == 2) {
                 const unsigned kb = wave_max_u32(am_key);
@@ -716,7 +710,7 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
                 }
             }
         } else if (b.want_trace && lane == 0) row_max_i[row] = -2;
-        STAMP(4)
+        FSTAMP(PROF_ARGMAX)
     }
     __syncthreads();
     if (tile_end > tile_beg && tile_beg + lane < tile_end && status == 0) {      // band geometry of the last (partial) tile
@@ -730,15 +724,15 @@ __device__ __forceinline__ void align_one(const DevBatch &b, const AlnDesc &d, A
     }
     (void)last_row;
 #ifdef ABPOA_HIP_PROFILE
-    for (int i_ = 0; i_ < 6; ++i_) seg_keep[i_] = seg[i_];
+    for (int i_ = 0; i_ < DIAG_SLOTS; ++i_) seg_keep[i_] = fseg[i_];
 #endif
     }   // general row loop
     TailState ts; ts.cursor = cursor; ts.n_cells = n_cells; ts.status = status; ts.rows_done = rows_done; ts.best_score = best_score; ts.best_i = best_i; ts.best_j = best_j;
     ts.clk0 = clk0; ts.clk1 = clk1;
 #ifdef ABPOA_HIP_PROFILE
-    for (int i_ = 0; i_ < 6; ++i_) ts.seg[i_] = seg_keep[i_];
+    for (int i_ = 0; i_ < DIAG_SLOTS; ++i_) ts.seg[i_] = seg_keep[i_];
 #else
-    for (int i_ = 0; i_ < 6; ++i_) ts.seg[i_] = 0;
+    for (int i_ = 0; i_ < DIAG_SLOTS; ++i_) ts.seg[i_] = 0;
 #endif
     finish_alignment<T, GAP>(b, d, out_rec, ts);
 }

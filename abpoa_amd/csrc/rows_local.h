@@ -245,7 +245,7 @@ __device__ __forceinline__ void rows_local(const DevBatch &b, const AlnDesc &d, 
         GLOBAL_AS AlnOut *o = vgpr_ptr(out_rec);
         o->status = status; o->n_cells = status == 0 ? (long long)imax(0, gn - 2) * W : 0; o->cells_used = status == 0 ? (long long)(gn - 1) * row_stride : 0;
         o->clk_dp = 0; o->n_rows_done = n_rows_done; o->best_score = best_score; o->best_row = best_i; o->best_col = best_j;
-        for (int i_ = 0; i_ < 6; ++i_) o->seg[i_] = 0;
+        for (int i_ = 0; i_ < DIAG_SLOTS; ++i_) o->seg[i_] = 0;
     }
     (void)status_cells; (void)o1; (void)o2; (void)qlen_sn;
 }
@@ -517,7 +517,7 @@ __device__ __forceinline__ void rows_local_team(const DevBatch &b, const AlnDesc
         GLOBAL_AS AlnOut *o = vgpr_ptr(out_rec);
         o->status = status; o->n_cells = status == 0 ? (long long)imax(0, gn - 2) * W : 0; o->cells_used = status == 0 ? (long long)(gn - 1) * row_stride : 0;
         o->clk_dp = 0; o->n_rows_done = n_rows_done; o->best_score = best_score; o->best_row = best_i; o->best_col = best_j;
-        for (int i_ = 0; i_ < 6; ++i_) o->seg[i_] = 0;
+        for (int i_ = 0; i_ < DIAG_SLOTS; ++i_) o->seg[i_] = 0;
     }
 }
 

@@ -118,3 +118,72 @@ def test_host_routing_rules(tmp_path):
                    capture_output=True)
     p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
     assert p.returncode == 0 and "host rules ok" in p.stdout, p.stdout
+
+
+DIAG_RULES = r"""
+// diag.h alone (no HIP header): the packed words of AlnOut.seg at their field limits, the bits of ABPOA_HIP_DBG, and their help text
+#include <stdio.h>
+#include <string.h>
+#include <string>
+#include "diag.h"
+#include "engine_options.h"
+using namespace abpoa_hip;
+static int fails = 0;
+#define CHECK(x) do { if (!(x)) { printf("FAILED: %s\n", #x); ++fails; } } while (0)
+int main() {
+    // census word: 24 bits of rows over 40 bits of ticks; what the kernels add per row is one row and its ticks
+    const long long R = (1ll << 24) - 1, T = (1ll << 40) - 1;
+    for (long long r : {0ll, 1ll, R}) for (long long t : {0ll, 1ll, T}) { const long long w = census_pack(r, t); CHECK(census_rows(w) == r && census_ticks(w) == t); }
+    { long long w = 0; for (int i = 0; i < 1000; ++i) w += census_pack(1, 12345); CHECK(census_rows(w) == 1000 && census_ticks(w) == 12345000); }
+    // census "why" word: three counts of 20 bits
+    const long long Y = (1ll << 20) - 1;
+    for (long long a : {0ll, 1ll, Y}) for (long long b : {0ll, 1ll, Y}) for (long long c : {0ll, 1ll, Y}) {
+        const long long w = census_why_pack(a, b, c); CHECK(census_why_many_preds(w) == a && census_why_declined(w) == b && census_why_beyond_ring(w) == c); }
+    CHECK(census_why_pack(1, 0, 0) + census_why_pack(0, 1, 0) + census_why_pack(0, 0, 1) == census_why_pack(1, 1, 1));
+    // wide body word: 32 bits of rows, 16 of int32 long-read rows, 15 of int16 ones
+    for (long long a : {0ll, 1ll, (1ll << 32) - 1}) for (long long b : {0ll, 1ll, (1ll << 16) - 1}) for (long long c : {0ll, 1ll, (1ll << 15) - 1}) {
+        const long long w = wide_body_pack(a, b, c); CHECK(w >= 0 && wide_body_rows(w) == a && wide_body_long32(w) == b && wide_body_long16(w) == c); }
+    // placement key: HW_ID (wave 0-3, simd 4-5, cu 8-11, sh 12, se 13-15) under XCC_ID; two waves share a SIMD iff xcc, se, sh, cu and simd agree
+    { const long long k = placement_pack(0xffffffffll, 15); CHECK((k & 0xffffffffll) == 0xffffffffll && (k >> 32) == 15);
+      CHECK(placement_simd(placement_pack(0x1234, 3)) == placement_simd(placement_pack(0x123f, 3)));          // another wave slot of the same SIMD
+      CHECK(placement_simd(placement_pack(0x1234, 3)) != placement_simd(placement_pack(0x1224, 3)));          // another SIMD
+      CHECK(placement_simd(placement_pack(0x1234, 3)) != placement_simd(placement_pack(0x1334, 3)));          // another CU
+      CHECK(placement_simd(placement_pack(0x1234, 3)) != placement_simd(placement_pack(0x1234, 4))); }        // another XCC
+    // the test hooks are 64 .. 2048, one bit each, and none of them is an ablation bit; the ablation names cover bits 0-5 in both loops
+    const int hooks[] = {DBG_NO_FAST_LOOPS, DBG_KEEP_ROW_SLOTS, DBG_WALK_REPORT, DBG_WALK_GIVES_UP, DBG_ONE_WAVE_BACKTRACK, DBG_CXX_TIGHT_LOOP};
+    int all = 0; for (int i = 0; i < 6; ++i) { CHECK(hooks[i] == 64 << i); CHECK(!(hooks[i] & DBG_ABLATION_BITS)); all |= hooks[i]; }
+    CHECK(all == 4032 && DBG_ABLATION_BITS == 63);
+    CHECK((ABL_NO_ARENA_STORE | ABL_FAST_NO_RING_STORE | ABL_FAST_NO_ARGMAX | ABL_FAST_NO_F_CLOSED_FORM | ABL_FAST_NO_GATHER | ABL_FAST_NO_SLOW_F) == DBG_ABLATION_BITS);
+    CHECK((ABL_NO_ARENA_STORE | ABL_GEN_FAKE_ARGMAX | ABL_GEN_LITERAL_F_SCAN | ABL_GEN_NO_CHUNKS | ABL_GEN_FAKE_GATHER | ABL_GEN_NO_QUERY_PROFILE) == DBG_ABLATION_BITS);
+    // every slot of every layout is one of the six; the clocks are four sums and the six slots
+    CHECK(DIAG_SLOTS == 6 && PLACE_KEY < DIAG_SLOTS && PROF_TOP == 5 && CEN_WHY == 5 && WC_DECLINED == 5 && DTAIL_WINDOW_TICKS == 5 && RTAIL_WINDOW_TICKS == 5 && WALK_STEPS == 5);
+    CHECK(CLK_SEG0 == 4 && CLK_SLOTS == 10);
+    // the help of ABPOA_HIP_DBG names every bit: each hook by its value, the ablations as a group
+    const char *names[128], *help[128]; const int n = list_options(names, help, 128); const char *h = nullptr;
+    for (int i = 0; i < n && i < 128; ++i) if (strcmp(names[i], "ABPOA_HIP_DBG") == 0) h = help[i];
+    CHECK(h != nullptr);
+    if (h) { int covered = 0;
+             for (const DbgBit &d : DBG_BITS) { const std::string tok = " " + std::to_string(d.value) + " "; CHECK(strstr(h, tok.c_str()) != nullptr); CHECK(strstr(h, d.what) != nullptr);
+                                                CHECK(!(covered & d.value)); covered |= d.value; }
+             CHECK(covered == (all | DBG_ABLATION_BITS)); printf("%s\n", h); }
+    printf(fails ? "diag rules: %d failed\n" : "diag rules ok\n", fails);
+    return fails ? 1 : 0;
+}
+"""
+
+
+def test_diag_words_bits_and_help(tmp_path):
+    """diag.h, the one definition of the kernels' diagnostic channel, as a stand-alone host program built with -fsanitize=undefined,address (as
+    tests/test_pass_ladder.py builds its own): the packed words of AlnOut.seg round-trip at their field limits (a census word of 2^24 - 1 rows has its top
+    bit set), the test-hook bits of ABPOA_HIP_DBG are 64 .. 2048 and disjoint from the ablation bits, and list_options' help names every bit."""
+    import shutil
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None:
+        pytest.skip("no C++ compiler")
+    src = tmp_path / "diag_rules.cpp"; src.write_text(DIAG_RULES)
+    exe = tmp_path / "diag_rules"
+    b = subprocess.run([cxx, "-O1", "-std=c++17", "-Wall", "-fsanitize=undefined,address", "-fno-sanitize-recover=undefined", "-I" + CSRC, "-o", str(exe), str(src),
+                        os.path.join(CSRC, "engine_options.cpp")], timeout=300, capture_output=True, text=True)
+    assert b.returncode == 0, b.stderr[-3000:]
+    p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0 and "diag rules ok" in p.stdout and "runtime error" not in p.stderr and "Sanitizer" not in p.stderr, (p.stdout[-3000:], p.stderr[-3000:])

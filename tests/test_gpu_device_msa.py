@@ -372,7 +372,7 @@ def test_long_read_rows_take_the_all_chunk_bodies(tmp_path):
         assert declined == 0, (job, rows)
         assert (long32 > 0 and long16 == 0) if bits == 32 else (long16 > 0 and long32 == 0), (job, rows)
     # The same library on the inputs of tests/test_gpu_wide_bodies.py (table: tests/wide_bands.py), through the flat API: the rows those tests compare with the
-    # oracle did take the all-chunk bodies.  abpoa_hip__debug_clocks slots 4 .. 9 = AlnOut.seg[0 .. 5] = rows per path (rows_fast.h WCOUNT): 0 all-chunk body
+    # oracle did take the all-chunk bodies.  abpoa_hip__debug_clocks slots 4 .. 9 = AlnOut.seg[0 .. 5] = rows per path (abpoa_amd/csrc/diag.h WideSlot): 0 all-chunk body
     # (a row of 9-11 chunks also in bits 32-47 / 48-62 for int32 / int16), 1 not eligible, 2 ring / geometry, 3 wider than the body's chunks, 4 vectors beyond
     # every predecessor's band outside the last chunk, 5 the body declined (arg-max key window, wrap guard).
     import json

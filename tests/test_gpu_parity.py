@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import helpers as H
-from gpu_harness import dir_counts, engine  # noqa: F401  (engine: the fixture)
+from gpu_harness import dir_counts, engine, launch, row_launches  # noqa: F401  (engine: the fixture)
 
 pytestmark = pytest.mark.gpu
 CASES = H.golden_cases()
@@ -162,6 +162,37 @@ def test_need_scores_redo_path(engine, monkeypatch):
     ref = api.msa_batch(sets, p, n_threads=4)
     for a, b_ in zip(dev, ref):
         assert a.status == 0 and b_.status == 0 and a.cons_seq == b_.cons_seq and a.cons_cov == b_.cons_cov
+
+
+_DEBUG_BIT_ITEMS = []
+
+
+def _debug_bit_items():
+    """(name, FlatCase, oracle output) of the first container of each golden the debug-bit test runs; the oracle runs once."""
+    if not _DEBUG_BIT_ITEMS:
+        for name in ("seq_lg_gb", "seq_ag_gb", "seq_cg_gb", "s1k_ag_gb", "s1k_cg_gb"):
+            case = H.FlatCase(H.first_golden(name))
+            _DEBUG_BIT_ITEMS.append((name, case, H.run_oracle(case)))
+    return _DEBUG_BIT_ITEMS
+
+
+def test_debug_bits_do_not_change_results(engine, monkeypatch):
+    """In the shipped library no bit of ABPOA_HIP_DBG changes a result: bits 0-5 are timing ablations that exist only in a library built with
+    -DABPOA_HIP_ABLATE (diag.h ABL), bits 7-9 choose what AlnOut.seg reports or make the direction-word walk give up so that the alignment is redone with
+    score records.  959 = bits 0-5 and 7-9, on the general kernel with its own fast-row path (ABPOA_HIP_NOFAST=1: no banded row loop in the launch plan),
+    on its general rows alone (1023: bit 6 as well) and on the fast row loops.  The first container of seq_lg_gb / seq_ag_gb / seq_cg_gb (the three
+    dp_kernel<GAP>) and of s1k_ag_gb / s1k_cg_gb (bands of ~70 columns: the rows the general kernel's fast-row path takes), each one launch with and without
+    the trace, against the oracle cell for cell; the first two forms launch no fast row kernel."""
+    for env, general_only in (({"ABPOA_HIP_NOFAST": "1", "ABPOA_HIP_DBG": "959"}, True), ({"ABPOA_HIP_DBG": "1023"}, True), ({"ABPOA_HIP_DBG": "959"}, False)):
+        monkeypatch.delenv("ABPOA_HIP_NOFAST", raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        row_launches(engine)
+        for name, case, o in _debug_bit_items():
+            for trace in (True, False):
+                launch([(name, case, o)], trace, "debug bits %s" % env)
+        n = row_launches(engine)
+        assert n == [0, 0, 0] if general_only else n[0] > 0, (env, n)
 
 
 def test_hip_batch_mixed_widths(engine):

@@ -15,7 +15,7 @@ lib = ffi.lib(); ffi.check(lib.abpoa_hip_init(0))
 cases = [H.FlatCase(g) for _ in range(N)]
 for c in cases: c.sc.ret_cigar = ret_cigar
 pbs = (ffi.Problem * N)(*[c.pb for c in cases]); res = (ffi.Result * N)()
-d = (C.c_longlong * 10)()
+d = (C.c_longlong * 10)()      # (abpoa_hip__debug_clocks: slots, layouts of d[4:] and the bits of ABPOA_HIP_DBG are abpoa_amd/csrc/diag.h)
 for it in range(3):
     for c in cases: c.reset()
     for i, c in enumerate(cases): pbs[i] = c.pb

@@ -1,3 +1,4 @@
+# (the ten clock slots read here and what d[4:] holds in which build: abpoa_amd/csrc/diag.h)
 import ctypes as C, sys, time
 import os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from abpoa_amd import api, ffi, synth
