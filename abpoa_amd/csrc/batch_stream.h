@@ -2,6 +2,7 @@
 //   prepare(shapes)  -> layout computed, pools grown, host slots handed out (pinned memory, zero copy)
 //   fill slots       -> caller writes each problem straight into its slot (any thread)
 //   run()            -> one H2D copy, one DP-kernel launch, one D2H copy, synchronise; overflowed arenas are retried
+//                       (every size, offset and routing answer it uses: batch_plan.h, host arithmetic tested without a GPU)
 //   rec()/cigar()    -> results read in place from pinned memory
 // Several BatchStreams may be driven concurrently from different host threads (one per read-set group);
 // the flat C API (abpoa_hip_align_batch) uses a process-wide default instance under a mutex.
@@ -11,15 +12,12 @@
 #include <hip/hip_runtime.h>
 #include "engine.h"
 #include "batch_types.h"
+#include "batch_plan.h"
 #include "../../include/abpoa_hip.h"
 
 namespace abpoa_hip {
 
-enum : unsigned {
-    BS_TRACE = 0x1,             // keep per-row arg-max, allow fetch_trace()
-    BS_FRESH_BAND = 0x2,        // max_pos_left/right start as (n_rows, 0) for every row: initialised on the device
-    BS_WANT_BAND_STATE = 0x4,   // copy max_pos_left/right back to the host
-};
+// (the BS_* flags of prepare(): batch_plan.h)
 
 struct Blob {                   // device buffer with optional pinned host mirror; grow-only
     uint8_t *dev = nullptr, *host = nullptr; size_t cap = 0; bool mirrored;
@@ -38,15 +36,15 @@ class BatchStream {
     int open(int device);
     void close();
     int prepare(const abpoa_hip_scoring_t *sc, int n, const BatchShape *shapes, unsigned flags);
-    ProblemSlots slots(int i) const;
+    ProblemSlots slots(int i) const { return problem_slots(I_, O_, desc_[i], in_.host, out_.host); }
     int run();
     int n() const { return n_; }
     const AlnOut &rec(int i) const { return recs_[i]; }
     const AlnDesc &desc(int i) const { return desc_[i]; }
-    const uint64_t *cigar(int i) const;
-    const int32_t *left(int i) const;
-    const int32_t *right(int i) const;
-    int fetch_trace(int i, const uint8_t *row_active, abpoa_hip_trace_t *T);   // after run(), BS_TRACE only
+    const uint64_t *cigar(int i) const { return (const uint64_t *)(out_.host + O_.cig) + desc_[i].cigar_off; }
+    const int32_t *left(int i) const { return (const int32_t *)(out_.host + O_.left) + desc_[i].row0; }
+    const int32_t *right(int i) const { return (const int32_t *)(out_.host + O_.right) + desc_[i].row0; }
+    int fetch_trace(int i, abpoa_hip_trace_t *T);   // after run(), BS_TRACE only
     StreamStats take_stats() { StreamStats s = stats_; stats_ = StreamStats(); return s; }
 
   private:
@@ -55,12 +53,13 @@ class BatchStream {
     Blob in_, out_, planes_;
     abpoa_hip_scoring_t sc_{}; std::vector<int32_t> mat_;
     unsigned flags_ = 0; int n_ = 0, P_ = 1;
-    // arena capacities (cells): score records full width / estimate, direction-plane arenas likewise
-    std::vector<AlnDesc> desc_; std::vector<AlnOut> recs_; std::vector<int64_t> full_cells_, est_cells_, dir_full_cells_, dir_est_cells_;
+    // the stages of a pass of run(): what it uploads (first pass / retry / kept band), and what it keeps of the records that came back
+    struct Pass { std::vector<int> todo; std::vector<AlnDesc> descs; DevBatch b; int n_fast = 0; bool first = true, dir = false; };
+    int upload_pass(const Pass &ps, std::vector<int32_t> &saved_lr);
+    int collect_pass(Pass &ps);
+    std::vector<AlnDesc> desc_; std::vector<AlnOut> recs_; std::vector<ArenaCells> cells_;
     std::vector<std::vector<uint8_t>> trace_arena_;     // BS_TRACE: arena of every finished alignment, copied out before a retry pass re-uses the device arenas
-    int64_t rows_tot_ = 0, preds_tot_ = 0, outs_tot_ = 0, q_tot_ = 0, cig_tot_ = 0;
-    size_t o_desc_ = 0, o_mat_ = 0, o_query_ = 0, o_base_ = 0, o_sdist_ = 0, o_pd_ = 0, o_nid_ = 0, o_rem_ = 0, o_act_ = 0, o_poff_ = 0, o_pred_ = 0, o_ooff_ = 0, o_out_ = 0, in_bytes_ = 0;
-    size_t o_rec_ = 0, o_left_ = 0, o_right_ = 0, o_bsn_ = 0, o_esn_ = 0, o_coff_ = 0, o_rmi_ = 0, o_cig_ = 0, out_bytes_ = 0;
+    PoolTotals tot_{}; InLayout I_{}; OutLayout O_{};      // pool sizes and the byte offsets of the pools in in_ / out_ (batch_plan.h)
     StreamStats stats_;
 };
 

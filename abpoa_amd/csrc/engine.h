@@ -1,4 +1,4 @@
-// Internal interface between the host engine (engine.cpp) and the device code (dp_kernel.hip).
+// Internal interface between the host engine (engine.cpp) and the device code (the kernel units dp_*.hip, poa_*.hip).
 // Not installed; the public C-ABI is include/abpoa_hip.h.
 #pragma once
 #include <stdint.h>
@@ -65,7 +65,7 @@ struct LdsPlan {
     int32_t bt_off, bt_bytes;     // arena tile (relative to phase_off)
     int32_t bt_bytes_tail;        // arena window of the fast path's tail kernel (bt_bytes is the general kernel's, which shares the region with its score ring)
     int32_t bt_wc;                // column-slice windows of the backtrack: columns per slice (0: the kernel's default)
-    // --- fast row loop (dp_kernel.hip rows_fast): packed H|E score ring [fr_rows][words][fr_cols + 4] dwords at phase_off + fr_off
+    // --- fast row loop (rows_fast.h, dp_fast_rows.hip): packed H|E score ring [fr_rows][words][fr_cols + 4] dwords at phase_off + fr_off
     int32_t fr_off, fr_rows, fr_cols;   // fr_rows: power of two <= 64; fr_cols: multiple of 64, 0 = fast loop disabled
     // --- wide row loop (one wavefront per alignment, rows_fast<.., WIDEB>): its own score ring [wfr_rows][words][wfr_cols + 4] at w_phase_off + fr_off;
     //     wx_off: end of that ring (relative to w_phase_off); wide_on = 0: not used by this launch
@@ -141,7 +141,7 @@ inline bool dir_words_allowed(const abpoa_hip_scoring_t *sc) {
 }
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
-// Fixed LDS structures of the kernel (rows per metadata tile, ring depths); see dp_kernel.hip.
+// Fixed LDS structures of the kernel (rows per metadata tile, ring depths); see dp_general.hip.
 int lds_fixed_bytes_dp();
 int lds_fixed_bytes_bt();
 // LDS carve-up of one launch and the wide row loop's workgroups per CU by its LDS (msa_device_plan.cpp: host arithmetic, no runtime call)

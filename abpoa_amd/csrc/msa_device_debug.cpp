@@ -6,6 +6,7 @@
 #include <string.h>
 #include "engine_options.h"
 #include "msa_device_debug.h"
+#include "batch_plan.h"
 
 namespace abpoa_hip {
 
@@ -123,6 +124,9 @@ void DeviceDebug::prepare_check(int k) {
             else complain("predecessor entries beyond the set's slots, set still ok:", n, (long long)want_pred.size(), S.pred_cap);
             if (p.out_off) { ooff.resize(n + 1); dl(ooff.data(), p.out_off + S.node0, 4 * (size_t)(n + 1)); outr.resize(std::max<size_t>(1, want_out.size()));
                              if ((long long)want_out.size() <= S.pred_cap) dl(outr.data(), p.out_row + S.pred0, 4 * want_out.size()); }
+            // row_pd / row_sdist of those lists as the flat driver's host code makes them (batch_plan.cpp: the one host definition)
+            std::vector<uint8_t> want_sdv(n); std::vector<uint32_t> want_pdv(2 * (size_t)n);
+            (void)fill_dir_tables(n, want_poff.data(), want_pred.data(), want_sdv.data(), want_pdv.data());
             for (int r = 0; r < n; ++r) {
                 const int u = order[r]; const PoaNode &h = G.node(u);
                 if (base[r] != h.base) complain("row_base", r, base[r], h.base);
@@ -130,17 +134,11 @@ void DeviceDebug::prepare_check(int k) {
                 const int want_rem = p.banded ? G.remain()[u] : 0;
                 if (rem[r] != want_rem) complain("remaining length", r, rem[r], want_rem);
                 if (poff[r] != want_poff[r]) complain("pred_off", r, poff[r], want_poff[r]);
-                const int np = want_poff[r + 1] - want_poff[r]; unsigned long long want_pd = ~0ull;
-                for (int t = 0; t < np; ++t) {
-                    const int pr = want_pred[want_poff[r] + t];
-                    if ((long long)want_pred.size() <= S.pred_cap && pred[want_poff[r] + t] != pr) complain("pred_row entry", r, pred[want_poff[r] + t], pr);
-                    if (t < 8 && r - pr <= 254) want_pd = (want_pd & ~(0xffull << (8 * t))) | ((unsigned long long)(r - pr) << (8 * t));
-                }
-                const unsigned long long got_pd = (unsigned long long)pd[2 * (size_t)r] | ((unsigned long long)pd[2 * (size_t)r + 1] << 32);
-                if (got_pd != want_pd) complain("row_pd (low dword shown)", r, (long long)(uint32_t)got_pd, (long long)(uint32_t)want_pd);
-                int far = 0; for (int t = 0; t < (int)h.out_id.size(); ++t) far = std::max(far, row[h.out_id[t]]);
-                const int want_sd = far >= n - 1 ? 255 : std::min(std::max(far - r, 0), 255);      // (the sink is the last row)
-                if (sd[r] != want_sd) complain("row_sdist", r, sd[r], want_sd);
+                if ((long long)want_pred.size() <= S.pred_cap) for (int t = want_poff[r]; t < want_poff[r + 1]; ++t)
+                    if (pred[t] != want_pred[t]) complain("pred_row entry", r, pred[t], want_pred[t]);
+                if (pd[2 * (size_t)r] != want_pdv[2 * (size_t)r] || pd[2 * (size_t)r + 1] != want_pdv[2 * (size_t)r + 1])
+                    complain("row_pd (low dword shown)", r, (long long)pd[2 * (size_t)r], (long long)want_pdv[2 * (size_t)r]);
+                if (sd[r] != want_sdv[r]) complain("row_sdist", r, sd[r], want_sdv[r]);
                 if (p.out_off) {
                     if (ooff[r] != want_ooff[r]) complain("out_off", r, ooff[r], want_ooff[r]);
                     if ((long long)want_out.size() <= S.pred_cap) for (int t = want_ooff[r]; t < want_ooff[r + 1]; ++t) if (outr[t] != want_out[t]) complain("out_row entry", r, outr[t], want_out[t]);

@@ -261,6 +261,49 @@ def test_arena_overflow_retry_keeps_traces(engine, monkeypatch):
     assert n >= 2
 
 
+def scoring_groups(prefixes):
+    """The banded global goldens whose label starts with one of `prefixes`, grouped by scoring: what one launch of the flat API can hold."""
+    groups = {}
+    for label, path in CASES:
+        if not label.startswith(prefixes):
+            continue
+        g = H.read_abpg(path)
+        if int(g["wb"][0]) < 0 or int(g["align_mode"][0]) != 0:
+            continue
+        key = (int(g["m"][0]), int(g["gap_mode"][0]), int(g["zdrop"][0]), tuple(g["mat"].tolist()), int(g["gap_open1"][0]), int(g["gap_ext1"][0]),
+               int(g["gap_open2"][0]), int(g["gap_ext2"][0]))
+        groups.setdefault(key, []).append((label, g))
+    return [items for items in groups.values() if len(items) >= 2]
+
+
+# Passes per call observed on an MI355X for the three groups (affine: 6 alignments, 4 of them on words; convex: 4, all on words; linear: 3, records) --
+# switch unset or 80: 1 / 1 / 1; 55: 2 / 1 / 1; 40, 30, 20: 2 / 1 / 2; 10, 5, 1: 2 / 2 / 2, goldens met at every value.  The words' estimate keeps
+# two vectors of slack per row, so the convex group overflows only once the band's share is nearly gone: 10 is the largest value tried at which all three retry
+WORDS_RETRY_PCT = "10"
+
+
+def test_arena_overflow_retry_under_direction_words(engine, monkeypatch):
+    """The same under-sized arenas without the trace, so the launches use direction-word arenas where the penalties allow: an alignment that overflows its
+    words' estimate runs again at full width in a second pass (engine.cpp collect_pass), and scores and cigars still equal the goldens.  Every call must
+    take exactly two passes (abpoa_hip_get_stats counts them in n_launches): one means nothing overflowed, three that a retried alignment ran once more."""
+    from abpoa_amd import ffi
+    monkeypatch.setenv("ABPOA_HIP_ARENA_PCT", WORDS_RETRY_PCT)
+    groups = scoring_groups(("seq_", "s1k_"))
+    assert len(groups) >= 2
+    walked = 0
+    dir_counts(engine)
+    for items in groups:
+        before = ffi.stats()["n_launches"]
+        outs = H.run_hip([H.FlatCase(g) for _, g in items], want_trace=False)
+        passes = ffi.stats()["n_launches"] - before
+        print("passes", passes, [label for label, _ in items])
+        for (label, g), o in zip(items, outs):
+            H.compare_with_golden(o, g, check_planes=False, label="overflow-retry under words " + label)
+        assert passes == 2, ([label for label, _ in items], passes)
+        walked += dir_counts(engine)[0]
+    assert walked > 0      # (some of the groups' penalties fit the words)
+
+
 @pytest.mark.parametrize("env", [{"ABPOA_HIP_RING_ROWS": "4"}, {"ABPOA_HIP_NOWIDE": "1"}, {"ABPOA_HIP_DIR_WIDE": "1"},
                                  {"ABPOA_HIP_DIR_WIDE": "1", "ABPOA_HIP_RING_ROWS": "4"}],
                          ids=["ring4_hbm_gather", "nowide", "dir_wide", "dir_wide_ring4"])
