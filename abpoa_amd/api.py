@@ -11,7 +11,7 @@ from . import ffi, seqio
 
 GLOBAL, LOCAL, EXTEND = 0, 1, 2
 LINEAR, AFFINE, CONVEX = 0, 1, 2
-OUT_CONS, OUT_MSA, AMB_STRAND, PROGRESSIVE = 1, 2, 4, 8
+OUT_CONS, OUT_MSA, AMB_STRAND, PROGRESSIVE, OUT_GFA = 1, 2, 4, 8, 0x10
 GUIDE_HITS, GUIDE_SKETCH = 0x01000000, 0x02000000
 
 
@@ -29,8 +29,8 @@ def check_guide_kw(k, w, is_aa=False):
     return guide_kw(k, w)
 
 
-def _batch_flags(params, out_cons, out_msa, amb_strand, progressive, mm_k, mm_w):
-    flags = (OUT_CONS if out_cons else 0) | (OUT_MSA if out_msa else 0) | (AMB_STRAND if amb_strand else 0)
+def _batch_flags(params, out_cons, out_msa, amb_strand, progressive, mm_k, mm_w, out_gfa=False):
+    flags = (OUT_CONS if out_cons else 0) | (OUT_MSA if out_msa else 0) | (AMB_STRAND if amb_strand else 0) | (OUT_GFA if out_gfa else 0)
     if progressive:
         flags |= PROGRESSIVE | check_guide_kw(mm_k, mm_w, params.m > 5)
     return flags
@@ -50,11 +50,16 @@ class GuideTiming(C.Structure):      # abpoa_hip_guide_timing_t
     _fields_ = [("sketch_ms", C.c_double), ("pair_ms", C.c_double), ("total_s", C.c_double), ("n_minimizers", C.c_int64)]
 
 
+class Gfa(C.Structure):              # abpoa_hip_gfa_t
+    _fields_ = [("n_seg", C.c_int32), ("n_link", C.c_int32), ("n_path", C.c_int32), ("seg_node", C.POINTER(C.c_int32)), ("seg_base", C.POINTER(C.c_uint8)),
+                ("link_off", C.POINTER(C.c_int32)), ("link_from", C.POINTER(C.c_int32)), ("path_off", C.POINTER(C.c_int64)), ("path_node", C.POINTER(C.c_int32))]
+
+
 class Msa(C.Structure):              # abpoa_hip_msa_t
     _fields_ = [("status", C.c_int32), ("n_reads", C.c_int32), ("cons_len", C.c_int32),
                 ("cons_base", C.POINTER(C.c_uint8)), ("cons_cov", C.POINTER(C.c_int32)), ("cons_node_id", C.POINTER(C.c_int32)),
                 ("msa_len", C.c_int32), ("msa_rows", C.c_int32), ("msa_base", C.POINTER(C.c_uint8)), ("n_cells", C.c_int64),
-                ("is_rc", C.POINTER(C.c_uint8))]
+                ("is_rc", C.POINTER(C.c_uint8)), ("gfa", C.POINTER(Gfa))]
 
 
 class MsaTiming(C.Structure):        # abpoa_hip_msa_timing_t
@@ -94,6 +99,15 @@ class Params:
                            float(self.wf), self.zdrop, 1, 0)
 
 
+class GfaView:
+    """The arrays of one abpoa_hip_gfa_t (include/abpoa_hip.h): ids are the printed ones, node id - 1."""
+    __slots__ = ("n_seg", "n_link", "n_path", "seg_node", "seg_base", "link_off", "link_from", "path_off", "path_node")
+
+    def __init__(self, *v):
+        for k, x in zip(self.__slots__, v):
+            setattr(self, k, x)
+
+
 class _BatchOut:
     """Owns the result records of one abpoa_hip_msa_batch call; the library's arrays are released when the last SetResult goes."""
     __slots__ = ("lib", "out", "n")
@@ -116,11 +130,11 @@ class _BatchOut:
 class SetResult:
     """Result of one read-set: a view of the library's record.  Strings / lists are built on first access (building 1000 Python
     strings and coverage lists eagerly costs more than the whole GPU job of a batch)."""
-    __slots__ = ("_o", "_owner", "_m", "_cons_seq", "_cov_list", "_msa_seq")
+    __slots__ = ("_o", "_owner", "_m", "_cons_seq", "_cov_list", "_msa_seq", "_gfa")
 
     def __init__(self, owner, rec, m):
         self._owner, self._o, self._m = owner, rec, m
-        self._cons_seq = self._cov_list = self._msa_seq = None
+        self._cons_seq = self._cov_list = self._msa_seq = self._gfa = None
 
     status = property(lambda self: self._o.status)
     is_rc = property(lambda self: [bool(self._o.is_rc[i]) for i in range(self._o.n_reads)] if self._o.is_rc else [False] * self._o.n_reads)
@@ -141,6 +155,25 @@ class SetResult:
             n = self._o.cons_len
             self._cov_list = np.frombuffer(C.string_at(self._o.cons_cov, 4 * n), dtype=np.int32).tolist() if n > 0 else []
         return self._cov_list
+
+    @property
+    def cons_node_id(self):
+        n = self._o.cons_len
+        return np.frombuffer(C.string_at(self._o.cons_node_id, 4 * n), dtype=np.int32) if n > 0 else np.zeros(0, np.int32)
+
+    @property
+    def gfa(self):
+        """abpoa_hip_gfa_t as numpy arrays (out_gfa=True), else None: n_seg, n_link, n_path, seg_node, seg_base, link_off, link_from, path_off, path_node."""
+        if self._gfa is None and self._o.gfa:
+            g = self._o.gfa.contents
+
+            def arr(ptr, n, dt):
+                return np.frombuffer(C.string_at(ptr, n * np.dtype(dt).itemsize), dtype=dt) if n > 0 else np.zeros(0, dt)
+            n_pn = int(g.path_off[g.n_path]) if g.n_path > 0 else 0
+            self._gfa = GfaView(g.n_seg, g.n_link, g.n_path, arr(g.seg_node, g.n_seg, np.int32), arr(g.seg_base, g.n_seg, np.uint8),
+                                arr(g.link_off, g.n_seg + 1, np.int32), arr(g.link_from, g.n_link, np.int32), arr(g.path_off, g.n_path + 1, np.int64),
+                                arr(g.path_node, n_pn, np.int32))
+        return self._gfa
 
     @property
     def msa_seq(self):
@@ -212,17 +245,18 @@ class EncodedSets:
 
 
 def msa_batch(read_sets, params, out_cons=True, out_msa=False, n_threads=0, lib=None, encoded=None, weights=None, amb_strand=False,
-              progressive=False, mm_k=0, mm_w=0):
+              progressive=False, mm_k=0, mm_w=0, out_gfa=False):
     """Consensus / MSA of many independent read-sets (lists of strings) in one call.
     Returns a list of SetResult.  `lib` defaults to the HIP engine (tests may pass the CPU shim).
     weights: per set, per read, per base edge weights (the reference's -Q); amb_strand: the reference's -s;
-    progressive: the reference's -p, reads aligned in guide-tree order (mm_k / mm_w: its -k / -w, 0 = default)."""
+    progressive: the reference's -p, reads aligned in guide-tree order (mm_k / mm_w: its -k / -w, 0 = default);
+    out_gfa: the graph as the reference's GFA output walks it (SetResult.gfa, format_gfa); the consensus then only with out_cons."""
     lib = lib or ffi.lib()
     _bind_msa(lib)
     enc = encoded or EncodedSets(read_sets, params.m, weights)
     out = (Msa * enc.n)()
     sc = params.scoring()
-    flags = _batch_flags(params, out_cons, out_msa, amb_strand, progressive, mm_k, mm_w)
+    flags = _batch_flags(params, out_cons, out_msa, amb_strand, progressive, mm_k, mm_w, out_gfa)
     rc = lib.abpoa_hip_msa_batch(C.byref(sc), enc.n, enc.sets, out, flags, n_threads)
     if rc != 0:
         raise ffi.EngineError(f"abpoa_hip_msa_batch failed ({rc}): {lib.abpoa_hip_last_error().decode() if hasattr(lib, 'abpoa_hip_last_error') else ''}")
@@ -256,11 +290,11 @@ class BatchContext:
     __del__ = close
 
     def msa_batch(self, read_sets, params, out_cons=True, out_msa=False, n_threads=0, encoded=None, weights=None, amb_strand=False, progressive=False,
-                  mm_k=0, mm_w=0):
+                  mm_k=0, mm_w=0, out_gfa=False):
         enc = encoded or EncodedSets(read_sets, params.m, weights)
         out = (Msa * enc.n)()
         sc = params.scoring()
-        flags = _batch_flags(params, out_cons, out_msa, amb_strand, progressive, mm_k, mm_w)
+        flags = _batch_flags(params, out_cons, out_msa, amb_strand, progressive, mm_k, mm_w, out_gfa)
         rc = self.lib.abpoa_hip_msa_batch_ctx(self.h, C.byref(sc), enc.n, enc.sets, out, flags, n_threads)
         if rc != 0:
             raise ffi.EngineError(f"abpoa_hip_msa_batch_ctx failed ({rc}): {self.lib.abpoa_hip_ctx_last_error(self.h).decode()}")
@@ -366,3 +400,32 @@ def format_output(result, names=None, out_cons=True, out_msa=False):
         lines.append(">Consensus_sequence")
         lines.append(result.cons_seq)
     return "\n".join(lines) + "\n"
+
+
+def format_gfa(result, names=None, out_cons=False):
+    """Text exactly as the reference prints a graph as GFA (abpoa_generate_gfa, src/abpoa_output.c:168-268; -r 3, with out_cons -r 4) from
+    SetResult.gfa: header, S / L lines in walk order, a P line per read (reversed with '-' where the read went in as its reverse complement)
+    and with out_cons the consensus path.  "" for an empty graph."""
+    g = result.gfa
+    if g is None or g.n_seg <= 0:
+        return ""
+    letters = seqio.AA_DECODE if result._m > 5 else seqio.NT_DECODE
+    out = ["H\tVN:Z:1.0\tNS:i:%d\tNL:i:%d\tNP:i:%d\n" % (g.n_seg, g.n_link, g.n_path + (1 if out_cons else 0))]
+    seg, base, lo, lf = g.seg_node.tolist(), g.seg_base.tolist(), g.link_off.tolist(), g.link_from.tolist()
+    for i, u in enumerate(seg):
+        out.append("S\t%d\t%s\n" % (u, letters[base[i]]))
+        for k in range(lo[i], lo[i + 1]):
+            out.append("L\t%d\t+\t%d\t+\t0M\n" % (lf[k], u))
+    po, rc = g.path_off.tolist(), result.is_rc
+    for i in range(g.n_path):
+        nm = names[i] if names and i < len(names) and names[i] else str(i + 1)
+        p = g.path_node[po[i]:po[i + 1]].tolist()
+        if rc[i]:
+            body = ",".join("%d-" % x for x in reversed(p))
+        else:
+            body = ",".join("%d+" % x for x in p)
+        out.append("P\t%s\t%s" % (nm, body + "\t*\n" if p else ""))
+    if out_cons:
+        ids = result.cons_node_id.tolist()
+        out.append("P\tConsensus_sequence\t" + (",".join("%d+" % (x - 1) for x in ids) + "\t*\n" if ids else ""))
+    return "".join(out)

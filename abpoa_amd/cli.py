@@ -5,14 +5,16 @@
   -m INT  alignment mode 0 global / 1 local / 2 extension        -M INT match   -X INT mismatch   -t FILE score matrix
   -O INT[,INT] gap open (O1,O2)   -E INT[,INT] gap extension (E1,E2)   -b INT / -f FLOAT adaptive band (b < 0: off)
   -c amino-acid input   -l input is a LIST of sequence files (one read-set each)   -o FILE output [stdout]
-  -r INT  0 consensus FASTA, 1 MSA (PIR), 2 both
+  -r INT  0 consensus FASTA, 1 MSA (PIR), 2 both, 5 consensus FASTQ
+  --gfa / --gfa-cons  the graph as GFA, exactly what the reference prints for -r 3 / -r 4 (--gfa-cons: with the consensus path);
+          instead of the -r output (not together with -r 1 / 2 / 5)
   -s  ambiguous strand: a read that aligns badly is tried as its reverse complement    -Q  FASTQ qualities as edge weights
   -p  progressive: align the reads of a set in the order of the guide tree built from their minimizers (global mode; no seeding)
   -k INT / -w INT  minimizer k-mer size / window of that guide tree [19 / 10; amino acids 7 / 4]
 
 With -l every file of the list is one read-set and ALL of them go through ONE abpoa_hip_msa_batch call (the reference
 loops over the files one at a time, src/abpoa.c:128-135); the output is the concatenation the reference prints.
-Options outside the engine (-S -i -d -g, -r 3/4/5) exit with an error rather than being ignored."""
+Options outside the engine (-S -i -d -g) exit with an error rather than being ignored; so do -r 3 / 4: the long options above are their spelling here."""
 import argparse
 import sys
 
@@ -47,13 +49,19 @@ def build_parser():
     ap.add_argument("-k", "--k-mer", type=int, default=0)       # (0: the reference's default for the alphabet)
     ap.add_argument("-w", "--window", type=int, default=0)
     ap.add_argument("--threads", type=int, default=0)
+    ap.add_argument("--gfa", action="store_true")
+    ap.add_argument("--gfa-cons", action="store_true")
     return ap
 
 
 def main(argv=None, lib=None, out=None):
     a = build_parser().parse_args(argv)
     if a.result not in (0, 1, 2, 5):
-        sys.stderr.write("abpoa_amd: -r %d (GFA output) is outside this engine\n" % a.result)
+        sys.stderr.write("abpoa_amd: -r %d (GFA output) is outside this engine%s\n" % (a.result, ": use --gfa / --gfa-cons" if a.result in (3, 4) else ""))
+        return 2
+    out_gfa = a.gfa or a.gfa_cons
+    if out_gfa and (a.result != 0 or (a.gfa and a.gfa_cons)):
+        sys.stderr.write("abpoa_amd: --gfa / --gfa-cons replace the -r output: give one of them, and no -r 1 / 2 / 5\n")
         return 2
     if a.progressive:
         try:
@@ -79,16 +87,18 @@ def main(argv=None, lib=None, out=None):
         sets.append(s)
         weights.append([seqio.qv_weights(x, y) for x, y in zip(s, q)])
     out_cons, out_msa, out_fq = a.result in (0, 2, 5), a.result in (1, 2), a.result == 5
+    if out_gfa:
+        out_cons = a.gfa_cons
     res = api.msa_batch(sets, params, out_cons=out_cons, out_msa=out_msa, n_threads=a.threads, lib=lib,
                         weights=weights if a.use_qual_weight else None, amb_strand=a.amb_strand,
-                        progressive=a.progressive, mm_k=a.k_mer, mm_w=a.window)
+                        progressive=a.progressive, mm_k=a.k_mer, mm_w=a.window, out_gfa=out_gfa)
     sink = out or (open(a.output, "w") if a.output else sys.stdout)
     try:
         for n, r in zip(names, res):
             if r.status != 0:
                 sys.stderr.write("abpoa_amd: alignment failed (status %d)\n" % r.status)
                 return 1
-            txt = api.format_output(r, n, out_cons, out_msa)
+            txt = api.format_gfa(r, n, out_cons) if out_gfa else api.format_output(r, n, out_cons, out_msa)
             if out_fq and r.cons_len > 0:      # -r 5: the consensus as FASTQ, a quality per base from its coverage (reference src/abpoa_output.c:270-276, :516-525)
                 import math
                 q = []

@@ -242,7 +242,7 @@ int run_msa_batch(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_rea
     if (n_groups <= 0) n_groups = opt_int("ABPOA_HIP_GROUPS", n_groups);
     if (n_groups <= 0) n_groups = n_sets >= 512 ? 4 : (n_sets >= 128 ? 2 : 1);
     if (n_groups > n_threads) n_groups = n_threads;
-    const bool want_msa = flags & ABPOA_HIP_OUT_MSA, want_cons = (flags & ABPOA_HIP_OUT_CONS) || !want_msa;
+    const bool want_msa = flags & ABPOA_HIP_OUT_MSA, want_gfa = flags & ABPOA_HIP_OUT_GFA, want_cons = (flags & ABPOA_HIP_OUT_CONS) || !(want_msa || want_gfa);
     const bool amb_strand = flags & ABPOA_HIP_AMB_STRAND;      // (any alphabet, as the reference: codes 0..3 are complemented, every other code becomes 4, src/abpoa_align.c:318-321)
     abpoa_hip_scoring_t scoring = *sc;
     if (sc->align_mode == ABPOA_HIP_LOCAL_MODE) scoring.wb = -1;        // reference abpoa_post_set_para, abpoa_align.c:150
@@ -255,7 +255,7 @@ int run_msa_batch(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_rea
         if (amb_strand) out[s].is_rc = (uint8_t *)calloc((size_t)std::max(1, sets[s].n_reads), 1);
     }
     std::vector<PoaGraph> graphs(n_sets);
-    for (int s = 0; s < n_sets; ++s) graphs[s].reset(sets[s].n_reads, want_msa);
+    for (int s = 0; s < n_sets; ++s) graphs[s].reset(sets[s].n_reads, want_msa || want_gfa);      // (read ids per edge: abpoa_post_set_para, src/abpoa_align.c:145)
 
     // ---- groups run concurrently, each with its own aligner (stream) and worker pool
     std::vector<std::unique_ptr<GroupAligner>> aligners;
@@ -279,9 +279,19 @@ int run_msa_batch(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_rea
     if (rc == ABPOA_HIP_OK) {
         const double t0 = now_s();
         Pool pool(n_threads);
+        std::atomic<int> no_mem{0};
         pool.run(n_sets, [&](int s) {
-            if (out[s].status != 0 || graphs[s].empty()) return;
+            if (out[s].status != 0) return;
             abpoa_hip_msa_t &o = out[s];
+            if (want_gfa) {                                          // (an empty graph: a record with n_seg = 0)
+                std::vector<int32_t> sn, lo, lf, pn; std::vector<uint8_t> sb; std::vector<int64_t> po;
+                try { graphs[s].gfa(&sn, &sb, &lo, &lf, &po, &pn); } catch (...) { o.status = ABPOA_HIP_EINVAL; return; }
+                o.gfa = gfa_alloc((int)sn.size(), (int)lf.size(), sets[s].n_reads, (int64_t)pn.size());
+                if (!o.gfa) { no_mem.store(1); return; }
+                memcpy(o.gfa->seg_node, sn.data(), 4 * sn.size()); memcpy(o.gfa->seg_base, sb.data(), sb.size()); memcpy(o.gfa->link_off, lo.data(), 4 * lo.size());
+                memcpy(o.gfa->link_from, lf.data(), 4 * lf.size()); memcpy(o.gfa->path_off, po.data(), 8 * po.size()); memcpy(o.gfa->path_node, pn.data(), 4 * pn.size());
+            }
+            if (graphs[s].empty()) return;
             std::vector<int> ids, cov; std::vector<uint8_t> bases;
             if (want_cons) {
                 graphs[s].consensus(&ids, &bases, &cov);
@@ -303,6 +313,7 @@ int run_msa_batch(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_rea
             }
         });
         if (tm) tm->cons_s = now_s() - t0;
+        if (no_mem.load()) rc = ABPOA_HIP_ENOMEM;
     }
     if (tm) { tm->total_s = now_s() - t_start; tm->n_threads = n_threads; tm->n_groups = n_groups; }
     if (rc != ABPOA_HIP_OK) for (int s = 0; s < n_sets; ++s) abpoa_hip_free_msa(&out[s]);
@@ -331,11 +342,52 @@ int abpoa_hip__last_aln(const uint8_t *seq0, int len0, int *out8, int reset) {
     if (reset) g_last_aln.clear();
     return found;
 }
+}
+namespace abpoa_hip {
+abpoa_hip_gfa_t *gfa_alloc(int n_seg, int n_link, int n_path, int64_t n_path_node) {
+    abpoa_hip_gfa_t *g = (abpoa_hip_gfa_t *)calloc(1, sizeof(*g));
+    if (!g) return nullptr;
+    g->n_seg = n_seg; g->n_link = n_link; g->n_path = n_path;
+    g->seg_node = (int32_t *)calloc((size_t)n_seg + 1, 4); g->seg_base = (uint8_t *)calloc((size_t)n_seg + 1, 1); g->link_off = (int32_t *)calloc((size_t)n_seg + 1, 4);
+    g->link_from = (int32_t *)calloc((size_t)n_link + 1, 4); g->path_off = (int64_t *)calloc((size_t)n_path + 1, 8); g->path_node = (int32_t *)calloc((size_t)n_path_node + 1, 4);
+    if (!g->seg_node || !g->seg_base || !g->link_off || !g->link_from || !g->path_off || !g->path_node) { gfa_free(g); return nullptr; }
+    return g;
+}
+void gfa_free(abpoa_hip_gfa_t *g) {
+    if (!g) return;
+    free(g->seg_node); free(g->seg_base); free(g->link_off); free(g->link_from); free(g->path_off); free(g->path_node); free(g);
+}
+}
+extern "C" {
+// reference abpoa_generate_gfa, src/abpoa_output.c:182-264 (letters: ab_char256_table, src/abpoa_seq.c)
+int abpoa_hip_format_gfa(const abpoa_hip_msa_t *r, int m, const char *const *names, int out_cons, FILE *fp) {
+    if (!r || !fp) return ABPOA_HIP_EINVAL;
+    const abpoa_hip_gfa_t *g = r->gfa;
+    if (!g || g->n_seg <= 0) return ABPOA_HIP_OK;
+    static const char nt_letter[] = "ACGTN-", aa_letter[] = "ACGTNBDEFHIJKLMOPQRSUVWXYZ*-";
+    const char *letter = m > 5 ? aa_letter : nt_letter; const int n_letter = m > 5 ? 28 : 6;
+    fprintf(fp, "H\tVN:Z:1.0\tNS:i:%d\tNL:i:%d\tNP:i:%d\n", g->n_seg, g->n_link, g->n_path + (out_cons ? 1 : 0));
+    for (int i = 0; i < g->n_seg; ++i) {
+        fprintf(fp, "S\t%d\t%c\n", g->seg_node[i], g->seg_base[i] < n_letter ? letter[g->seg_base[i]] : '*');
+        for (int k = g->link_off[i]; k < g->link_off[i + 1]; ++k) fprintf(fp, "L\t%d\t+\t%d\t+\t0M\n", g->link_from[k], g->seg_node[i]);
+    }
+    for (int i = 0; i < g->n_path; ++i) {
+        if (names && names[i] && names[i][0]) fprintf(fp, "P\t%s\t", names[i]); else fprintf(fp, "P\t%d\t", i + 1);
+        const int64_t lo = g->path_off[i], hi = g->path_off[i + 1];
+        if (r->is_rc && r->is_rc[i]) for (int64_t j = hi - 1; j >= lo; --j) fprintf(fp, j != lo ? "%d-," : "%d-\t*\n", g->path_node[j]);
+        else for (int64_t j = lo; j < hi; ++j) fprintf(fp, j != hi - 1 ? "%d+," : "%d+\t*\n", g->path_node[j]);
+    }
+    if (out_cons) {
+        fprintf(fp, "P\tConsensus_sequence\t");
+        for (int i = 0; i < r->cons_len; ++i) fprintf(fp, i != r->cons_len - 1 ? "%d+," : "%d+\t*\n", r->cons_node_id[i] - 1);
+    }
+    return ABPOA_HIP_OK;
+}
 void abpoa_hip_free_msa_array(abpoa_hip_msa_t *r, int n) { for (int i = 0; r && i < n; ++i) abpoa_hip_free_msa(&r[i]); }
 void abpoa_hip_free_msa(abpoa_hip_msa_t *r) {
     if (!r) return;
-    free(r->cons_base); free(r->cons_cov); free(r->cons_node_id); free(r->msa_base); free(r->is_rc);
-    r->cons_base = nullptr; r->cons_cov = nullptr; r->cons_node_id = nullptr; r->msa_base = nullptr; r->is_rc = nullptr;
+    free(r->cons_base); free(r->cons_cov); free(r->cons_node_id); free(r->msa_base); free(r->is_rc); abpoa_hip::gfa_free(r->gfa);
+    r->gfa = nullptr; r->cons_base = nullptr; r->cons_cov = nullptr; r->cons_node_id = nullptr; r->msa_base = nullptr; r->is_rc = nullptr;
     r->cons_len = r->msa_len = r->msa_rows = 0;
 }
 }

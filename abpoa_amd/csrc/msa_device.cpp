@@ -80,19 +80,20 @@ struct Arena {                 // grow-only device / pinned-host buffers kept ac
         return audit_allocation(host, n, "pinned staging buffer");
     }
 };
-struct Cache { Arena in, graph, rows, planes, out, msa; hipStream_t stream = nullptr, copy_stream = nullptr; hipEvent_t ev_copy = nullptr;
+struct Cache { Arena in, graph, rows, planes, out, msa, gfa; hipStream_t stream = nullptr, copy_stream = nullptr; hipEvent_t ev_copy = nullptr;
         std::vector<hipEvent_t> ev; int device = -1;
         // frees every pool (the caller has made `device` the current one)
-        void release() { for (Arena *a : {&in, &graph, &rows, &planes, &out, &msa}) { if (a->dev) (void)hipFree(a->dev); if (a->host) (void)hipHostFree(a->host);
+        void release() { for (Arena *a : {&in, &graph, &rows, &planes, &out, &msa, &gfa}) { if (a->dev) (void)hipFree(a->dev); if (a->host) (void)hipHostFree(a->host);
                 *a = Arena(); } } };
 Cache g_cache[MSA_DEVICE_SLOTS]; std::mutex g_cache_mu[MSA_DEVICE_SLOTS];      // one per worker of the multi-device batch call
 
 struct Layout {                // byte offsets inside the three device blobs
     // in blob (uploaded): sets, read tables, reads, score matrix
     // (o_rc, o_wrc: device only, behind the uploaded part)
-    size_t o_sets, o_roff, o_rlen, o_reads, o_mat, o_rargs, o_msaoff_h, o_wts, in_bytes, o_rc, o_wrc, in_dev_bytes;
+    size_t o_sets, o_roff, o_rlen, o_reads, o_mat, o_rargs, o_msaoff_h, o_gfaoff_h, o_wts, in_bytes, o_rc, o_wrc, in_dev_bytes;
     // graph blob (device only, the tail of it downloaded at the end): per-node pools
-    size_t o_cnode, o_ccov, o_cbase, o_isrc;
+    size_t o_cnode, o_ccov, o_cbase, o_isrc, o_gcnt;
+    size_t o_gwalk, o_gorw, o_goff;      // GFA output (GfaDev): walk order, ORed read bitsets, the host's offsets -- zero bytes unless the job asked for it
     size_t o_state, o_base, o_nin, o_nout, o_naln, o_in, o_out, o_outw, o_inx, o_outx, o_outwx, o_aln, o_nread, o_row, o_order0, o_order1, o_rid, o_mrank,
             o_msaoff, o_tout, o_toutw, o_tin, graph_bytes;
     // rows blob: DP inputs / outputs per row, descriptors, cigars, scratch
@@ -108,6 +109,8 @@ struct Job {
     PoaDev p; DevBatch b, b_rc, b_r;      // kernel arguments of the graph kernels and of the row loops (b_rc: the -s retry, b_r: the all-rounds kernel)
     bool dbg_sync, use_rounds; size_t rounds_lds;
     std::vector<int64_t> msa_off;
+    GfaDev g; std::vector<int64_t> gfa_off;      // GFA output: kernel arguments; per set first segment, first link, first path entry, path capacity
+    size_t go_seg, go_loff, go_lfrom, go_poff, go_pnode, go_base, go_cnt, go_bytes; int64_t gfa_d2h;      // byte offsets of the result pools in Cache.gfa
     double t_begin, t_queue, t_done;
 };
 
@@ -160,6 +163,7 @@ void lay_out(const DevicePlan &pl, int n_sets, bool any_w, Layout &L, size_t *dl
     // (o_rargs, o_msaoff_h: host-side staging only)
     L.o_sets = take(sizeof(PoaSet) * n_sets); L.o_roff = take(8 * (pl.tot_reads + 1)); L.o_rlen = take(4 * (pl.tot_reads + 1)); L.o_mat = take(4 * sc->m * sc->m);
     L.o_rargs = take(poa_rounds_args_bytes()); L.o_msaoff_h = take(pl.want_msa ? 8 * (size_t)n_sets : 0);
+    L.o_gfaoff_h = take(pl.want_gfa ? 32 * (size_t)n_sets : 0);
     L.o_wts = take(any_w ? 4 * (size_t)(pl.tot_bases + 64) : 0);      // (per-base weights, -Q: in front of the reads, so that they go up with the first part)
     L.o_reads = take(pl.tot_bases + 64); L.in_bytes = o;      // reads last: they go up in two parts
     // -s: reverse complements / reversed weights of the reads under retry
@@ -168,6 +172,7 @@ void lay_out(const DevicePlan &pl, int n_sets, bool any_w, Layout &L, size_t *dl
     L.o_state = take(sizeof(PoaState) * n_sets);
     // downloaded part first, contiguous: per-set state and the consensus results
     L.o_cnode = take(4 * pl.cons_tot); L.o_ccov = take(4 * pl.cons_tot); L.o_cbase = take(pl.cons_tot); L.o_isrc = take(pl.amb ? (size_t)pl.tot_reads : 0);
+    L.o_gcnt = take(pl.want_gfa ? 12 * (size_t)n_sets : 0);
     *dl_bytes = o;
     L.o_order0 = take(4 * pl.node_tot); L.o_order1 = take(4 * pl.node_tot); L.o_base = take(pl.node_tot); L.o_nout = take(pl.node_tot);
     L.o_out = take(4 * pl.node_tot * POA_HOT); L.o_outw = take(4 * pl.node_tot * POA_HOT); L.o_nread = take(4 * pl.node_tot);
@@ -177,6 +182,7 @@ void lay_out(const DevicePlan &pl, int n_sets, bool any_w, Layout &L, size_t *dl
     L.o_row = take(4 * pl.node_tot);
     L.o_rid = take(8 * pl.node_tot * (size_t)pl.out_cap * (size_t)pl.rid_words); L.o_mrank = take(pl.want_msa ? 4 * pl.node_tot : 0);
     L.o_msaoff = take(pl.want_msa ? 8 * (size_t)n_sets : 0);
+    L.o_gwalk = take(pl.want_gfa ? 4 * pl.node_tot : 0); L.o_gorw = take(pl.want_gfa ? 8 * pl.node_tot * (size_t)pl.rid_words : 0); L.o_goff = take(pl.want_gfa ? 32 * (size_t)n_sets : 0);
     L.o_tout = take(4 * pl.term_tot); L.o_toutw = take(4 * pl.term_tot); L.o_tin = take(4 * pl.term_tot);
     L.graph_bytes = o;
     o = 0;
@@ -319,6 +325,14 @@ void fill_poa_dev(Job &J) {
         p.out_fwd = (AlnOut *)(dr + L.o_outfwd); p.cigar_fwd = (uint64_t *)(dr + L.o_cigfwd);
     }
     p.cons_node = (int32_t *)(dg + L.o_cnode); p.cons_cov = (int32_t *)(dg + L.o_ccov); p.cons_base = dg + L.o_cbase;
+    // GFA output: the walk's counters and queue in LDS for graphs of up to 6000 nodes (48 KB), in memory above that and with ABPOA_HIP_ORDER_LDS=0
+    // (ABPOA_HIP_ORDER_CAP as for the order / rank walks); the result pools are laid out once the walk has counted (queue_job)
+    memset(&J.g, 0, sizeof(J.g));
+    if (pl.want_gfa) {
+        J.g.lds_cap = opt_int("ABPOA_HIP_ORDER_LDS", 1) ? std::min(((pl.max_node_cap + 3) & ~3), 6000) : 0;
+        { const int cap_ = opt_int("ABPOA_HIP_ORDER_CAP", -1); if (cap_ >= 0) J.g.lds_cap = std::min(J.g.lds_cap, cap_ & ~3); }
+        J.g.walk = (int32_t *)(dg + L.o_gwalk); J.g.cnt = (int32_t *)(dg + L.o_gcnt); J.g.orw = (uint64_t *)(dg + L.o_gorw); J.g.off = (const int64_t *)(dg + L.o_goff);
+    }
 }
 
 // ---- stage 6: arguments of the row-loop kernels (b_rc: the -s retry in the general kernel)
@@ -459,6 +473,13 @@ int queue_job(Job &J, DeviceDebug &dbg) {
     // ---- consensus on the device, then one small download: per-set state + consensus (node ids, bases, coverage)
     if (pl.want_cons) { HIP_OK(launch_poa_consensus(p, st), ABPOA_HIP_ELAUNCH); if (stage("consensus", pl.max_reads)) return ABPOA_HIP_ELAUNCH; }
     if (pl.want_msa) { HIP_OK(launch_poa_msa_rank(p, st), ABPOA_HIP_ELAUNCH); if (stage("msa rank", pl.max_reads)) return ABPOA_HIP_ELAUNCH; }
+    hipEvent_t *eg = C.ev.data() + 4 * pl.max_reads + 4;      // (four events behind the rounds': fit_device makes 4 * max_reads + 8)
+    if (pl.want_gfa) {      // GFA output, phase 1: the walk order and the segment / link counts of every set (they come down with the state block)
+        HIP_OK(hipEventRecord(eg[0], st), ABPOA_HIP_ELAUNCH);
+        HIP_OK(launch_poa_gfa_walk(p, J.g, st), ABPOA_HIP_ELAUNCH);
+        HIP_OK(hipEventRecord(eg[1], st), ABPOA_HIP_ELAUNCH);
+        if (stage("gfa walk", pl.max_reads)) return ABPOA_HIP_ELAUNCH;
+    }
     HIP_OK(hipMemcpyAsync(hg, dg, J.dl_bytes, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);
     HIP_OK(hipStreamSynchronize(st), ABPOA_HIP_ELAUNCH);
     // ---- MSA rows (reference abpoa_generate_rc_msa, src/abpoa_output.c:123-166): the rank pass left the column count of every set in its state; the results
@@ -479,6 +500,41 @@ int queue_job(Job &J, DeviceDebug &dbg) {
             if (stage("msa fill", pl.max_reads)) return ABPOA_HIP_ELAUNCH;
             HIP_OK(hipMemcpyAsync(C.msa.host, C.msa.dev, (size_t)msa_total, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);
             HIP_OK(hipStreamSynchronize(st), ABPOA_HIP_ELAUNCH);
+        }
+    }
+    // ---- GFA output, phase 2 (reference abpoa_generate_gfa, src/abpoa_output.c:168-268): segment, link and path pools of the sets back to back -- a path
+    //      has room for the bases of its set's reads, the kernel counts what it writes -- one upload of the offsets, the fill kernel, one download of the pools
+    J.go_bytes = 0; J.gfa_d2h = 0;
+    if (pl.want_gfa) {
+        const PoaState *hs_ = (const PoaState *)(hg + L.o_state); const int32_t *hc = (const int32_t *)(hg + L.o_gcnt);
+        J.gfa_off.assign(4 * (size_t)J.n_sets, 0);
+        int64_t seg_tot = 0, link_tot = 0, path_tot = 0;
+        for (int s = 0; s < J.n_sets; ++s) {
+            int64_t *o4 = J.gfa_off.data() + 4 * (size_t)s; o4[0] = seg_tot; o4[1] = link_tot; o4[2] = path_tot; o4[3] = 0;
+            if (hs_[s].status != POA_ST_OK || hs_[s].n_nodes <= 2 || hc[3 * s] <= 0) continue;
+            for (int r = 0; r < J.sets[s].n_reads; ++r) o4[3] += J.sets[s].lens[r];
+            seg_tot += hc[3 * s]; link_tot += hc[3 * s + 1]; path_tot += o4[3];
+        }
+        if (seg_tot > 0) {
+            size_t o = 0;
+            auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes); return at; };
+            J.go_seg = take(4 * (size_t)seg_tot); J.go_loff = take(4 * (size_t)(seg_tot + J.n_sets)); J.go_lfrom = take(4 * (size_t)link_tot);
+            J.go_poff = take(8 * (size_t)(pl.tot_reads + J.n_sets)); J.go_pnode = take(4 * (size_t)path_tot); J.go_base = take((size_t)seg_tot);
+            J.go_cnt = take(12 * (size_t)J.n_sets); J.go_bytes = o;
+            if ((rc = C.gfa.need_dev(J.go_bytes)) || (rc = C.gfa.need_host(J.go_bytes))) return rc;
+            memcpy(hi + L.o_gfaoff_h, J.gfa_off.data(), 32 * (size_t)J.n_sets);
+            HIP_OK(hipMemcpyAsync(dg + L.o_goff, hi + L.o_gfaoff_h, 32 * (size_t)J.n_sets, hipMemcpyHostToDevice, st), ABPOA_HIP_ELAUNCH);
+            uint8_t *dq = C.gfa.dev;
+            J.g.seg_node = (int32_t *)(dq + J.go_seg); J.g.link_off = (int32_t *)(dq + J.go_loff); J.g.link_from = (int32_t *)(dq + J.go_lfrom);
+            J.g.path_off = (int64_t *)(dq + J.go_poff); J.g.path_node = (int32_t *)(dq + J.go_pnode); J.g.seg_base = dq + J.go_base;
+            HIP_OK(hipEventRecord(eg[2], st), ABPOA_HIP_ELAUNCH);
+            HIP_OK(launch_poa_gfa_fill(p, J.g, st), ABPOA_HIP_ELAUNCH);
+            HIP_OK(hipEventRecord(eg[3], st), ABPOA_HIP_ELAUNCH);
+            if (stage("gfa fill", pl.max_reads)) return ABPOA_HIP_ELAUNCH;
+            HIP_OK(hipMemcpyAsync(C.gfa.host, dq, J.go_cnt, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);
+            HIP_OK(hipMemcpyAsync(C.gfa.host + J.go_cnt, dg + L.o_gcnt, 12 * (size_t)J.n_sets, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);      // (the fill kernel's flags)
+            HIP_OK(hipStreamSynchronize(st), ABPOA_HIP_ELAUNCH);
+            J.gfa_d2h = (int64_t)J.go_bytes;
         }
     }
     J.t_done = now_s();
@@ -531,6 +587,12 @@ void fill_stats(const Job &J, DeviceRunStats *stats) {
                     tmax / (tall / J.n_sets));
         }
     }
+    if (pl.want_gfa) {
+        hipEvent_t *eg = C.ev.data() + 4 * pl.max_reads + 4;
+        (void)hipEventElapsedTime(&ms, eg[0], eg[1]); stats->gfa_walk_ms = ms;
+        if (J.go_bytes) { (void)hipEventElapsedTime(&ms, eg[2], eg[3]); stats->gfa_fill_ms = ms; }
+        stats->gfa_d2h_bytes = J.gfa_d2h;
+    }
     stats->n_rounds = pl.max_reads > 0 ? pl.max_reads - 1 : 0; stats->device_s = J.t_done - J.t_queue;
 }
 
@@ -550,6 +612,9 @@ void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::
             // (only for a set that finished here: the record of a set that goes to another pass or to the host driver is overwritten there)
             if (pl.amb && hs[s].status == POA_ST_OK) { o_.is_rc = (uint8_t *)calloc((size_t)std::max(1, J.sets[s].n_reads), 1);
                     if (o_.is_rc) memcpy(o_.is_rc, hg + L.o_isrc + pl.ps[s].read0, (size_t)J.sets[s].n_reads); }
+            // (GFA output: the fill kernel's links or paths did not fit what the walk counted / the reads' bases: the set is redone like one whose walk failed)
+            const bool gfa_bad = pl.want_gfa && J.go_bytes && hs[s].status == POA_ST_OK && ((const int32_t *)(C.gfa.host + J.go_cnt))[3 * s + 2] != 0;
+            if (gfa_bad) { need_fb[s] = 1; free(o_.is_rc); o_.is_rc = nullptr; continue; }
             if (hs[s].status != POA_ST_OK) { need_fb[s] = 1;
                     if (J.dbg_sync) fprintf(stderr, "[poa-device] set %d falls back to the host driver: reason %d, %d nodes of %d\n", s, hs[s].reason,
                     hs[s].n_nodes, pl.ps[s].node_cap); continue; }
@@ -565,6 +630,22 @@ void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::
                 memcpy(o_.cons_base, h_cbase + c0, len); memcpy(o_.cons_cov, h_ccov + c0, 4 * (size_t)len);
                 memcpy(o_.cons_node_id, h_cnode + c0, 4 * (size_t)len);
             }
+            if (pl.want_gfa) {      // (an empty graph: a record with n_seg = 0, as the host driver leaves it)
+                const int32_t *hc = (const int32_t *)(hg + L.o_gcnt); const uint8_t *hq = C.gfa.host;
+                const bool any = hs[s].n_nodes > 2 && J.go_bytes && hc[3 * s] > 0;
+                const int n_seg = any ? hc[3 * s] : 0, n_link = any ? hc[3 * s + 1] : 0, nr = J.sets[s].n_reads;
+                const int64_t *o4 = J.gfa_off.data() + 4 * (size_t)s;
+                const int64_t *poff = any ? (const int64_t *)(hq + J.go_poff) + pl.ps[s].read0 + s : nullptr;
+                const int64_t n_pn = any ? std::min<int64_t>(std::max<int64_t>(0, poff[nr]), o4[3]) : 0;
+                o_.gfa = gfa_alloc(n_seg, n_link, nr, n_pn);
+                if (o_.gfa && any) {
+                    memcpy(o_.gfa->seg_node, (const int32_t *)(hq + J.go_seg) + o4[0], 4 * (size_t)n_seg); memcpy(o_.gfa->seg_base, hq + J.go_base + o4[0], (size_t)n_seg);
+                    memcpy(o_.gfa->link_off, (const int32_t *)(hq + J.go_loff) + o4[0] + s, 4 * ((size_t)n_seg + 1));
+                    memcpy(o_.gfa->link_from, (const int32_t *)(hq + J.go_lfrom) + o4[1], 4 * (size_t)n_link);
+                    memcpy(o_.gfa->path_off, poff, 8 * ((size_t)nr + 1)); memcpy(o_.gfa->path_node, (const int32_t *)(hq + J.go_pnode) + o4[2], 4 * (size_t)n_pn);
+                }
+                if (!o_.gfa) o_.status = ABPOA_HIP_ENOMEM;
+            }
             if (pl.want_msa && hs[s].n_nodes > 2) {      // (an empty graph has no MSA: the host driver leaves the record zeroed too)
                 const int len = std::max(0, hs[s].msa_len);
                 o_.msa_len = len; o_.msa_rows = J.sets[s].n_reads + (pl.want_cons ? 1 : 0);
@@ -574,6 +655,7 @@ void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::
         }
     });
     dbg.msa_check(hs, out);
+    dbg.gfa_check(hs, out);
     dbg.consensus_check(hs, out);
     // (a set with a node out of edge slots gains nothing from a pass with more node slots: the caller takes it to the last pass -- `roomy` above -- at once,
     //  and to the host driver if that was this one: a terminal with more than POA_TERM_MAX edges)
@@ -635,7 +717,7 @@ static int run_msa_device_body(const abpoa_hip_scoring_t *sc_in, int n_sets, con
     fill_poa_dev(J);
     if ((rc = fill_dev_batch(J, want_general))) return rc;
     plan_rounds(J);
-    DeviceDebug dbg(&J.p, &J.pl.ps, sets, n_sets, J.pl.sc.m, J.pl.aln_cap, J.pl.max_reads, J.pl.want_msa, J.pl.amb, J.C->stream);      // (ABPOA_HIP_DEVSYNC=1; msa_device_debug.h)
+    DeviceDebug dbg(&J.p, &J.pl.ps, sets, n_sets, J.pl.sc.m, J.pl.aln_cap, J.pl.max_reads, J.pl.want_msa, J.pl.amb, J.C->stream, J.pl.want_gfa);      // (ABPOA_HIP_DEVSYNC=1; msa_device_debug.h)
     if ((rc = queue_job(J, dbg))) return rc;
     fill_stats(J, stats);
     std::vector<char> need_fb;

@@ -17,6 +17,7 @@ struct DeviceRunStats {
     double rounds_ms, rounds_rows_share, rounds_mean_over_max; int32_t rounds_launches, pad2;
     int64_t rounds_algo_bytes;     // algorithmic bytes of the cells computed inside the all-rounds kernel
     double rounds_mticks[4];      // mean per set: 10^6 shader-clock ticks in prepare / row loop / backtrack / fuse
+    double gfa_walk_ms, gfa_fill_ms; int64_t gfa_d2h_bytes;      // GFA output (poa_gfa.hip): its two kernels, the bytes of its result download
 };
 
 // true when the scoring / output options can run on the device-resident path: every gap model and alignment mode (the fast row loops for banded global and

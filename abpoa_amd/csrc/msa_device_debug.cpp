@@ -42,10 +42,10 @@ void consensus_flat(int n, const int32_t *order, const uint8_t *base, const uint
 
 DeviceDebug::DeviceDebug(const PoaDev *p, const std::vector<PoaSet> *ps, const abpoa_hip_readset_t *sets, int n_sets, int m, int aln_cap, int max_reads,
         bool want_msa,
-                         bool amb, hipStream_t stream)
+                         bool amb, hipStream_t stream, bool want_gfa)
     : p_(p), ps_(ps), sets_(sets), n_sets_(n_sets), m_(m), aln_cap_(aln_cap), max_reads_(max_reads), want_msa_(want_msa), amb_(amb), st_(stream) {
-    on_ = opt_on("ABPOA_HIP_DEVSYNC");
-    if (on_) { graphs_.resize(std::min(n_sets, 4)); for (size_t i = 0; i < graphs_.size(); ++i) graphs_[i].reset(sets[i].n_reads, want_msa); }
+    on_ = opt_on("ABPOA_HIP_DEVSYNC"); want_gfa_ = want_gfa;
+    if (on_) { graphs_.resize(std::min(n_sets, 4)); for (size_t i = 0; i < graphs_.size(); ++i) graphs_[i].reset(sets[i].n_reads, want_msa || want_gfa); }
 }
 
 int DeviceDebug::stage(const char *what, int k) {
@@ -320,6 +320,21 @@ void DeviceDebug::msa_check(const PoaState *hs, const abpoa_hip_msa_t *out) {
         bool same = ml == out[s].msa_len;
         for (int r = 0; same && r < sets[s].n_reads; ++r) same = memcmp(rows[r].data(), out[s].msa_base + (size_t)r * ml, (size_t)ml) == 0;
         fprintf(stderr, "[poa-device]   set %d: msa check %s (device %d columns, host %d)\n", s, same ? "ok" : "FAILED", out[s].msa_len, ml);
+    }
+}
+
+// the device's GFA record of the first sets against the host routine on the host graph that was fed the same cigars
+void DeviceDebug::gfa_check(const PoaState *hs, const abpoa_hip_msa_t *out) {
+    if (!on_ || !want_gfa_) return;
+    for (int s = 0; s < (int)graphs_.size(); ++s) {
+        if (hs[s].status != POA_ST_OK || hs[s].n_nodes <= 2 || !out[s].gfa) continue;
+        std::vector<int32_t> sn, lo, lf, pn; std::vector<uint8_t> sb; std::vector<int64_t> po;
+        try { graphs_[s].gfa(&sn, &sb, &lo, &lf, &po, &pn); } catch (...) { fprintf(stderr, "[poa-device]   set %d: host gfa walk failed\n", s); continue; }
+        const abpoa_hip_gfa_t &g = *out[s].gfa;
+        bool same = g.n_seg == (int)sn.size() && g.n_link == (int)lf.size() && g.n_path == (int)po.size() - 1 && g.path_off[g.n_path] == (int64_t)pn.size();
+        same = same && !memcmp(g.seg_node, sn.data(), 4 * sn.size()) && !memcmp(g.seg_base, sb.data(), sb.size()) && !memcmp(g.link_off, lo.data(), 4 * lo.size())
+               && !memcmp(g.link_from, lf.data(), 4 * lf.size()) && !memcmp(g.path_off, po.data(), 8 * po.size()) && !memcmp(g.path_node, pn.data(), 4 * pn.size());
+        fprintf(stderr, "[poa-device]   set %d: gfa check %s (device %d segments, %d links; host %zu, %zu)\n", s, same ? "ok" : "FAILED", g.n_seg, g.n_link, sn.size(), lf.size());
     }
 }
 

@@ -18,7 +18,7 @@ class DeviceDebug {
 public:
     // p: the driver's kernel-argument record (its pointers stay valid for the run); ps: the per-set table
     DeviceDebug(const PoaDev *p, const std::vector<PoaSet> *ps, const abpoa_hip_readset_t *sets, int n_sets, int m, int aln_cap, int max_reads, bool want_msa, bool amb,
-                hipStream_t stream);
+                hipStream_t stream, bool want_gfa = false);
     bool on() const { return on_; }
     int stage(const char *what, int k);                     // synchronise and report; != 0: the stream is in error
     void order_check(int k);                                // row order of round k against the host graph's Kahn walk (order_mode 1)
@@ -27,8 +27,9 @@ public:
     void balance_report(int k, const DevBatch &b, hipEvent_t rows_begin, hipEvent_t rows_end);      // ABPOA_HIP_IMBAL: slowest / mean alignment of the round, censuses
     void msa_check(const PoaState *hs, const abpoa_hip_msa_t *out);
     void consensus_check(const PoaState *hs, const abpoa_hip_msa_t *out);
+    void gfa_check(const PoaState *hs, const abpoa_hip_msa_t *out);      // the device's GFA record against PoaGraph::gfa on the host graph fed the same cigars
 private:
-    bool on_; const PoaDev *p_; const std::vector<PoaSet> *ps_; const abpoa_hip_readset_t *sets_; int n_sets_, m_, aln_cap_, max_reads_; bool want_msa_, amb_; hipStream_t st_;
+    bool on_; const PoaDev *p_; const std::vector<PoaSet> *ps_; const abpoa_hip_readset_t *sets_; int n_sets_, m_, aln_cap_, max_reads_; bool want_msa_, amb_, want_gfa_ = false; hipStream_t st_;
     std::vector<PoaGraph> graphs_;      // host graphs of the first (up to four) sets
     std::vector<double> tot_set_; double sum_max_ = 0;      // balance_report: what lock-step costs over the rounds
 };

@@ -158,7 +158,7 @@ void job_sizes(DevicePlan &P, int n_sets, const abpoa_hip_readset_t *sets, int64
         P.tot_bases += sum; *max_cap0 = std::max(*max_cap0, std::min<int64_t>(2 + sum, 2 + (int64_t)(P.node_factor * mx) + 1024));
     }
     P.w_max = P.sc.wb + (int)(P.sc.wf * (float)P.max_qlen);
-    P.aln_cap = std::max(1, P.sc.m - 1); P.rid_words = P.want_msa ? std::max(1, (P.max_reads + 63) / 64) : 0;
+    P.aln_cap = std::max(1, P.sc.m - 1); P.rid_words = (P.want_msa || P.want_gfa) ? std::max(1, (P.max_reads + 63) / 64) : 0;
 }
 
 // Which kernels: the fast row loops (rows_fast.h: banded global, affine / convex; rows_local.h: local, int16, up to 575 columns) or -- `general` -- the
@@ -305,7 +305,7 @@ DevicePlan plan_device_job(const abpoa_hip_scoring_t *sc_in, int n_sets, const a
     const abpoa_hip_scoring_t *sc = &P.sc;
     // -s: low-scoring reads are aligned again as their reverse complement (poa_device.hip poa_strand_check_kernel)
     P.amb = flags & ABPOA_HIP_AMB_STRAND;
-    P.want_msa = flags & ABPOA_HIP_OUT_MSA; P.want_cons = (flags & ABPOA_HIP_OUT_CONS) || !P.want_msa;
+    P.want_msa = flags & ABPOA_HIP_OUT_MSA; P.want_gfa = flags & ABPOA_HIP_OUT_GFA; P.want_cons = (flags & ABPOA_HIP_OUT_CONS) || !(P.want_msa || P.want_gfa);
     // values per DP column in an arena of score records: one padded cell record of the fast loops (4 / 8 values) = the planes of the general kernel (engine.cpp
     //  pv)
     P.CW = record_values(sc->gap_mode);

@@ -14,7 +14,7 @@ namespace abpoa_hip {
 struct DevicePlan {
     abpoa_hip_scoring_t sc;        // the job's scoring; local mode: wb = -1 (reference abpoa_post_set_para, src/abpoa_align.c:150)
     double node_factor;
-    bool local, extend, unbanded, amb, want_msa, want_cons;
+    bool local, extend, unbanded, amb, want_msa, want_cons, want_gfa;      // want_gfa: ABPOA_HIP_OUT_GFA -- read ids per edge as for the MSA, walk / output pools
     int CW, DB;                    // values per cell record (engine.h record_values); bytes per direction word
     int max_reads, max_qlen, w_max, aln_cap, rid_words; int64_t tot_reads, tot_bases;
     // which kernels: the general kernel for every alignment / the local row loop / direction words / linear gaps on the narrow loop / the all-rounds kernel

@@ -43,6 +43,7 @@ GroupAligner *make_hip_aligner() {
     return a.release();
 }
 abpoa_hip_msa_timing_t g_timing;
+abpoa_hip_gfa_timing_t g_gfa_timing;      // GFA output of the last batch call (process-wide, like g_timing)
 
 bool strict_mode() { return opt_on("ABPOA_HIP_STRICT"); }
 void free_all(abpoa_hip_msa_t *out, int n) { for (int s = 0; s < n; ++s) abpoa_hip_free_msa(&out[s]); }
@@ -52,6 +53,7 @@ void add_stats(DeviceRunStats &t, const DeviceRunStats &d) {
     t.device_s += d.device_s; t.cons_s += d.cons_s; t.total_s += d.total_s;
     t.n_cells += d.n_cells; t.algo_bytes += d.algo_bytes; t.n_alignments += d.n_alignments; t.n_rounds += d.n_rounds;
     t.rounds_ms += d.rounds_ms; t.rounds_launches += d.rounds_launches; t.rounds_algo_bytes += d.rounds_algo_bytes;
+    t.gfa_walk_ms += d.gfa_walk_ms; t.gfa_fill_ms += d.gfa_fill_ms; t.gfa_d2h_bytes += d.gfa_d2h_bytes;
 }
 
 PassHints g_hints;      // start passes by job shape, for as long as the process lives (msa_passes.h)
@@ -189,6 +191,7 @@ void fill_timing(const QueueRun &Q, DeviceRunStats &tot, int n_threads, size_t n
     ss.kernel_ms = tot.rows_ms; ss.tail_ms = tot.tail_ms;
     ss.rounds_ms = tot.rounds_ms; ss.rounds_launches = tot.rounds_launches; ss.rounds_algo_bytes = tot.rounds_algo_bytes;
     add_global_stats(ss);
+    g_gfa_timing.walk_ms = tot.gfa_walk_ms; g_gfa_timing.fill_ms = tot.gfa_fill_ms; g_gfa_timing.d2h_bytes = tot.gfa_d2h_bytes;
     memset(&tm, 0, sizeof(tm));
     tm.engine_s = tot.device_s; tm.cons_s = tot.cons_s; tm.total_s = tot.total_s;
     tm.n_rounds = tot.n_rounds; tm.n_threads = n_threads; tm.n_groups = n_q;
@@ -271,7 +274,21 @@ struct PermutedSets {
     }
 };
 // MSA row r of the ordered run is input read order[r]: row order[r] of what the caller gets; the consensus row stays last
+// ... and GFA path r is the path of input read order[r] (the graph's read ids are positions in the guide order; P line i must be input read i)
+int paths_to_input_order(abpoa_hip_msa_t &o, const int32_t *order) {
+    abpoa_hip_gfa_t *g = o.gfa;
+    if (o.status != ABPOA_HIP_OK || !g || g->n_path <= 0) return ABPOA_HIP_OK;
+    const int n = g->n_path; const int64_t tot = g->path_off[n];
+    int64_t *off = (int64_t *)calloc((size_t)n + 1, 8); int32_t *node = (int32_t *)calloc((size_t)tot + 1, 4);
+    if (!off || !node) { free(off); free(node); return ABPOA_HIP_ENOMEM; }
+    for (int r = 0; r < n; ++r) off[order[r] + 1] = g->path_off[r + 1] - g->path_off[r];
+    for (int i = 0; i < n; ++i) off[i + 1] += off[i];
+    for (int r = 0; r < n; ++r) memcpy(node + off[order[r]], g->path_node + g->path_off[r], 4 * (size_t)(g->path_off[r + 1] - g->path_off[r]));
+    free(g->path_off); free(g->path_node); g->path_off = off; g->path_node = node;
+    return ABPOA_HIP_OK;
+}
 int rows_to_input_order(abpoa_hip_msa_t &o, const int32_t *order) {
+    if (const int rc = paths_to_input_order(o, order)) return rc;
     if (o.status != ABPOA_HIP_OK || !o.msa_base || o.msa_len <= 0 || o.msa_rows < o.n_reads) return ABPOA_HIP_OK;
     const size_t len = (size_t)o.msa_len;
     uint8_t *rows = (uint8_t *)malloc((size_t)o.msa_rows * len);
@@ -292,7 +309,7 @@ void note_guide_timing(const GuideResult &G) {
 int msa_batch_entry(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, abpoa_hip_msa_t *out, unsigned flags,
                     int n_threads, abpoa_hip_msa_timing_t &tm, int ctx_device, int ctx_slot) {
     if (!(flags & ABPOA_HIP_PROGRESSIVE)) return msa_batch_impl(sc, n_sets, sets, out, flags & ~ABPOA_HIP_GUIDE_KW(0xff, 0xff), n_threads, tm, ctx_device, ctx_slot);      // (k / w mean nothing without the flag)
-    const unsigned plain = flags & (ABPOA_HIP_OUT_CONS | ABPOA_HIP_OUT_MSA | ABPOA_HIP_AMB_STRAND);
+    const unsigned plain = flags & (ABPOA_HIP_OUT_CONS | ABPOA_HIP_OUT_MSA | ABPOA_HIP_OUT_GFA | ABPOA_HIP_AMB_STRAND);
     GuideParams gp;
     if (!sc || guide_params(sc->m, flags, &gp) != ABPOA_HIP_OK) { set_err("guide order: k-mer size / window outside 1..28 (amino acids 1..11) / 1..255"); return ABPOA_HIP_EINVAL; }
     if (sc->align_mode != ABPOA_HIP_GLOBAL_MODE || n_sets <= 0 || !sets || !out) return msa_batch_impl(sc, n_sets, sets, out, plain, n_threads, tm, ctx_device, ctx_slot);
@@ -362,6 +379,7 @@ int abpoa_hip_msa_batch(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_h
     return abpoa_hip::msa_batch_entry(sc, n_sets, sets, out, flags, n_threads, abpoa_hip::g_timing, -1, -1);
 }
 void abpoa_hip_get_msa_timing(abpoa_hip_msa_timing_t *out) { *out = abpoa_hip::g_timing; }
+void abpoa_hip_get_gfa_timing(abpoa_hip_gfa_timing_t *out) { if (out) *out = abpoa_hip::g_gfa_timing; }
 // ---- contexts
 abpoa_hip_ctx_t *abpoa_hip_ctx_create(int device) {
     using namespace abpoa_hip;

@@ -5,6 +5,7 @@
 //     dp_fast_kernel       banded DP row loop                                                          [dp_kernel.hip]
 //     dp_fast_tail_kernel  global best + backtrack -> graph cigar                                      [dp_kernel.hip]
 //     poa_fuse_kernel      cigar -> graph (abpoa_add_graph_alignment) + incremental row order          [poa_device.hip]
+// and, after the last round, the outputs: consensus, MSA rank / fill [poa_device.hip], GFA walk / fill [poa_gfa.hip].
 // One wavefront (= one workgroup) owns one read-set.  Internal interface between msa_device.cpp and the kernels.
 #pragma once
 #include <stdint.h>
@@ -109,6 +110,19 @@ struct PoaDev {                    // everything the poa_* kernels need; passed 
     AlnOut *out_fwd; uint64_t *cigar_fwd;    // forward result of a set under retry (cigar_fwd: same slices as cigar)
     int32_t *msa_rank; uint8_t *msa_out; const int64_t *msa_off;      // msa_off[set]: first byte of the set's rows in msa_out (host prefix sum over rows x msa_len)
 };
+
+// GFA output (poa_gfa.hip; ABPOA_HIP_OUT_GFA): what its two kernels need beside PoaDev.  Pools exist only in a job that asked for it.
+struct GfaDev {
+    int32_t lds_cap, pad;          // node capacity of the walk kernel's LDS tables (counters, queue: 8 bytes a node); larger graphs keep them in memory
+    int32_t *walk;                 // [node0 + i]: the node popped i-th by the reference's FIFO Kahn walk, source and sink left out (walk kernel; its queue while it runs)
+    int32_t *cnt;                  // [3 * set]: segments, links (walk kernel), 1 if the fill kernel's links or paths did not fit the host's layout
+    uint64_t *orw;                 // [(node0 + i) * rid_words]: the reads that leave the i-th segment, its out-edges' bitsets ORed (fill kernel's scratch)
+    const int64_t *off;            // [4 * set]: first segment, first link, first path entry of the set in the pools below; its path entries at most
+    int32_t *seg_node; uint8_t *seg_base; int32_t *link_off, *link_from;      // link_off: n_seg + 1 entries per set, at first segment + set
+    int64_t *path_off; int32_t *path_node;                                     // path_off: n_reads + 1 entries per set, at read0 + set, relative to the set's first entry
+};
+hipError_t launch_poa_gfa_walk(const PoaDev &p, const GfaDev &g, hipStream_t s);
+hipError_t launch_poa_gfa_fill(const PoaDev &p, const GfaDev &g, hipStream_t s);
 
 hipError_t launch_poa_init(const PoaDev &p, hipStream_t s);
 hipError_t launch_poa_prepare(const PoaDev &p, hipStream_t s);

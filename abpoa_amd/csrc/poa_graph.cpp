@@ -1,5 +1,6 @@
 // Host partial-order graph: see poa_graph.h for the reference line ranges each routine is pinned to.
 #include "poa_graph.h"
+#include <algorithm>
 #include <limits.h>
 #include <string.h>
 #include <stdexcept>
@@ -280,6 +281,40 @@ void PoaGraph::rc_msa(int m, int *msa_len, std::vector<std::vector<uint8_t>> *ro
                 num &= num - 1;
             }
         }
+    }
+}
+
+// reference abpoa_generate_gfa, src/abpoa_output.c:168-229: a plain Kahn walk with a FIFO queue (no aligned-group rule), ended by the sink
+void PoaGraph::gfa(std::vector<int32_t> *seg_node, std::vector<uint8_t> *seg_base, std::vector<int32_t> *link_off, std::vector<int32_t> *link_from,
+                   std::vector<int64_t> *path_off, std::vector<int32_t> *path_node) const {
+    const int n = (int)nodes_.size();
+    seg_node->clear(); seg_base->clear(); link_off->assign(1, 0); link_from->clear(); path_off->assign((size_t)tot_reads_ + 1, 0); path_node->clear();
+    if (n <= 2 || !use_read_ids_) return;
+    std::vector<int> deg(n), q; q.reserve(n);
+    for (int i = 0; i < n; ++i) deg[i] = nodes_[i].in_id.size();
+    std::vector<uint64_t> on((size_t)words_);
+    std::vector<std::vector<uint64_t>> seg_reads;      // per segment: the reads that leave it, all out-edges ORed
+    q.push_back(SRC);
+    bool done = false;
+    for (size_t head = 0; head < q.size(); ++head) {
+        const int cur = q[head];
+        if (cur == SINK) { done = true; break; }
+        const PoaNode &c = nodes_[cur];
+        if (cur != SRC) {
+            seg_node->push_back(cur - 1); seg_base->push_back(c.base);
+            for (int i = 0; i < c.in_id.size(); ++i) if (c.in_id[i] != SRC) link_from->push_back(c.in_id[i] - 1);
+            link_off->push_back((int32_t)link_from->size());
+            std::fill(on.begin(), on.end(), 0);
+            const std::vector<uint64_t> &ids = read_ids_[cur];
+            for (int e = 0; e < c.out_id.size(); ++e) for (int wd = 0; wd < words_; ++wd) on[wd] |= ids[(size_t)e * words_ + wd];
+            seg_reads.push_back(on);
+        }
+        for (int i = 0; i < c.out_id.size(); ++i) if (--deg[c.out_id[i]] == 0) q.push_back(c.out_id[i]);
+    }
+    if (!done) throw std::runtime_error("error in the GFA walk");
+    for (int r = 0; r < tot_reads_; ++r) {
+        for (size_t i = 0; i < seg_reads.size(); ++i) if (seg_reads[i][r >> 6] >> (r & 63) & 1) path_node->push_back((*seg_node)[i]);
+        (*path_off)[(size_t)r + 1] = (int64_t)path_node->size();
     }
 }
 

@@ -94,6 +94,11 @@ class PoaGraph {
     // Row-column MSA (reads only): n_reads rows of msa_len codes, gap = m.  Requires use_read_ids.
     void rc_msa(int m, int *msa_len, std::vector<std::vector<uint8_t>> *rows, std::vector<int> *node_col) const;
 
+    // The graph as the reference's GFA output walks it (abpoa_hip_gfa_t, include/abpoa_hip.h): segments in FIFO Kahn order, their in-links, one path per read.
+    // Requires use_read_ids; an empty graph leaves everything empty (path_off: tot_reads + 1 zeros).
+    void gfa(std::vector<int32_t> *seg_node, std::vector<uint8_t> *seg_base, std::vector<int32_t> *link_off, std::vector<int32_t> *link_from,
+             std::vector<int64_t> *path_off, std::vector<int32_t> *path_node) const;
+
     const std::vector<int> &index_to_node() const { return index_to_node_; }
     const std::vector<int> &node_to_index() const { return node_to_index_; }
     const std::vector<int> &remain() const { return remain_; }

@@ -16,10 +16,13 @@
  *     -z INT z-drop of extension mode [-1: off]   -e INT end bonus (accepted; as in the reference, nothing in the DP reads it)
  *     -c amino acids   -l the input is a list of files   -o FILE output [stdout]   -r INT 0 consensus, 1 MSA, 2 both, 5 consensus as FASTQ
  *     -s ambiguous strand   -Q base qualities as edge weights   -T INT host threads [all]   -v version
+ *     --gfa / --gfa-cons   the graph as GFA, the reference's text for -r 3 / -r 4 (abpoa_generate_gfa, src/abpoa_output.c:168-268; --gfa-cons: with the
+ *                          consensus path), instead of the -r output: not together with -r 1 / 2 / 5
  *     --piece INT files per GPU call with -l [2048]   --readers INT reader threads [8]      (no reference counterpart)
  * Degenerate inputs as the reference treats them: a file without records prints nothing; a record without bases after the first one is an MSA row
  * of gaps and adds nothing to the graph; a first record without bases ends the run as abpoa_add_graph_sequence does (src/abpoa_graph.c:487).
- * Options of the reference that the engine does not cover (-S -k -w -n -p -i -g -d -q, -r 3/4) are refused, not ignored.
+ * Options of the reference that the engine does not cover (-S -k -w -n -p -i -g -d -q) are refused, not ignored; so are the digits -r 3 / 4, whose
+ * spelling here is --gfa / --gfa-cons.  GFA output of a file that has records without bases is refused too.
  *
  * Plain C99 + zlib; links against libabpoa_hip.so only.  Own code throughout: no klib / kseq.
  */
@@ -158,7 +161,7 @@ static const struct option long_opt[] = {
     {"window", 1, NULL, 'w'}, {"min-poa-win", 1, NULL, 'n'}, {"progressive", 0, NULL, 'p'}, {"use-qual-weight", 0, NULL, 'Q'}, {"amino-acid", 0, NULL, 'c'},
     {"in-list", 0, NULL, 'l'}, {"increment", 1, NULL, 'i'}, {"amb-strand", 0, NULL, 's'}, {"output", 1, NULL, 'o'}, {"result", 1, NULL, 'r'}, {"out-pog", 1, NULL, 'g'},
     {"max-num-cons", 1, NULL, 'd'}, {"min-freq", 1, NULL, 'q'}, {"threads", 1, NULL, 'T'}, {"help", 0, NULL, 'h'}, {"version", 0, NULL, 'v'},
-    {"piece", 1, NULL, 1001}, {"readers", 1, NULL, 1002}, {0, 0, 0, 0}};
+    {"piece", 1, NULL, 1001}, {"readers", 1, NULL, 1002}, {"gfa", 0, NULL, 1003}, {"gfa-cons", 0, NULL, 1004}, {0, 0, 0, 0}};
 
 static void rs_free(readset_t *r) {
     for (int i = 0; i < r->n; ++i) { free(r->name[i]); free(r->code[i]); free(r->weight[i]); }
@@ -220,7 +223,7 @@ int main(int argc, char **argv) {
     const int timing = getenv("ABPOA_BATCH_TIMING") != NULL;      /* per piece on stderr: wait for the readers, the batch call, output */
     const double t_start = now_s();
     int mode = 0, match = 2, mismatch = 4, o1 = 4, o2 = 24, e1 = 2, e2 = 1, wb = 10, m = 5, in_list = 0, out_cons = 1, out_msa = 0, amb = 0, use_qv = 0, threads = 0, c;
-    int piece_sets = 2048, readers = 8, zdrop = -1, out_fq = 0;
+    int piece_sets = 2048, readers = 8, zdrop = -1, out_fq = 0, out_gfa = 0, gfa_cons = 0, r_given = 0;
     float wf = 0.01f; const char *mat_fn = NULL; char *s;
     while ((c = getopt_long(argc, argv, "m:M:X:t:O:E:b:f:z:e:QSk:w:n:i:clpso:r:g:d:q:T:hvV:", long_opt, NULL)) >= 0) {
         switch (c) {
@@ -241,16 +244,20 @@ int main(int argc, char **argv) {
             case 'T': threads = atoi(optarg); break;
             case 1001: piece_sets = atoi(optarg); if (piece_sets < 1) DIE("--piece must be at least 1"); break;
             case 1002: readers = atoi(optarg); break;
+            case 1003: out_gfa += 1; break;
+            case 1004: out_gfa += 1; gfa_cons = 1; break;
             case 'o': if (strcmp(optarg, "-") != 0 && freopen(optarg, "wb", stdout) == NULL) DIE("failed to open the output file %s", optarg); break;
-            case 'r': { const int r = atoi(optarg); if (r == 0) { out_cons = 1; out_msa = 0; } else if (r == 1) { out_cons = 0; out_msa = 1; } else if (r == 2) { out_cons = out_msa = 1; }
+            case 'r': { const int r = atoi(optarg); r_given = r; if (r == 0) { out_cons = 1; out_msa = 0; } else if (r == 1) { out_cons = 0; out_msa = 1; } else if (r == 2) { out_cons = out_msa = 1; }
                         else if (r == 5) { out_cons = 1; out_msa = 0; out_fq = 1; }      /* consensus as FASTQ: a quality per base from its coverage */
-                        else { fprintf(stderr, "abpoa_batch: -r %d (GFA output) is outside this engine\n", r); return 2; } } break;
+                        else { fprintf(stderr, "abpoa_batch: -r %d (GFA output) is outside this engine%s\n", r, (r == 3 || r == 4) ? ": use --gfa / --gfa-cons" : ""); return 2; } } break;
             case 'v': printf("abpoa_batch (MI355X engine; output of abPOA 1.4.1)\n"); return 0;
             case 'V': break;
-            case 'h': fprintf(stderr, "usage: abpoa_batch [-m -M -X -t -O -E -b -f -z -e -c -l -o -r -s -Q -T --piece --readers] <in.fa|in.fq|list.txt>   (see the head of abpoa_batch.c)\n"); return 1;
+            case 'h': fprintf(stderr, "usage: abpoa_batch [-m -M -X -t -O -E -b -f -z -e -c -l -o -r -s -Q -T --gfa --gfa-cons --piece --readers] <in.fa|in.fq|list.txt>   (see the head of abpoa_batch.c)\n"); return 1;
             default: fprintf(stderr, "abpoa_batch: option -%c is outside this engine (seeding, guide tree, incremental graphs, plots, multiple consensus)\n", c); return 2;
         }
     }
+    if (out_gfa && (out_gfa > 1 || r_given != 0)) { fprintf(stderr, "abpoa_batch: --gfa / --gfa-cons replace the -r output: give one of them, and no -r 1 / 2 / 5\n"); return 2; }
+    if (out_gfa) { out_cons = gfa_cons; out_msa = 0; out_fq = 0; }
     if (argc - optind != 1) { fprintf(stderr, "usage: abpoa_batch [options] <in.fa|in.fq|list.txt>\n"); return 1; }
     init_tables();
     const uint8_t *tbl = m > 5 ? aa_code : nt_code; const char *letter = m > 5 ? aa_letter : nt_letter;
@@ -264,7 +271,7 @@ int main(int argc, char **argv) {
     sc.gap_open1 = o1; sc.gap_ext1 = e1; sc.gap_open2 = o2; sc.gap_ext2 = e2;
     sc.align_mode = mode; sc.gap_mode = o1 == 0 ? ABPOA_HIP_LINEAR_GAP : ((o1 > 0 && o2 == 0) ? ABPOA_HIP_AFFINE_GAP : ABPOA_HIP_CONVEX_GAP);
     sc.wb = mode == ABPOA_HIP_LOCAL_MODE ? -1 : wb; sc.wf = wf; sc.zdrop = zdrop; sc.ret_cigar = 1; sc.rev_cigar = 0;
-    const unsigned flags = (out_cons ? ABPOA_HIP_OUT_CONS : 0u) | (out_msa ? ABPOA_HIP_OUT_MSA : 0u) | (amb ? ABPOA_HIP_AMB_STRAND : 0u);
+    const unsigned flags = (out_cons ? ABPOA_HIP_OUT_CONS : 0u) | (out_msa ? ABPOA_HIP_OUT_MSA : 0u) | (amb ? ABPOA_HIP_AMB_STRAND : 0u) | (out_gfa ? ABPOA_HIP_OUT_GFA : 0u);
 
     FILE *lf = in_list ? fopen(argv[optind], "r") : NULL;
     if (in_list && !lf) DIE("cannot open list %s", argv[optind]);
@@ -322,7 +329,10 @@ int main(int argc, char **argv) {
             if (set_of[i] < 0) continue;
             const abpoa_hip_msa_t *o = &out[set_of[i]];
             if (o->status != ABPOA_HIP_OK) DIE("alignment failed for input %ld (status %d)", file_no, o->status);
-            if (out_msa) {
+            if (out_gfa) {      /* (names: the records' own, after the sticky rule above; the formatter prints i + 1 for an empty one) */
+                if (n_kept[i] != r->n) DIE("input %ld: GFA output of a file with records without bases is outside this engine", file_no);
+                if (abpoa_hip_format_gfa(o, m, (const char *const *)r->name, out_cons, stdout) != ABPOA_HIP_OK) DIE("GFA output failed for input %ld", file_no);
+            } else if (out_msa) {
                 if (o->msa_len <= 0) continue;
                 int k = 0;                                               /* next kept record */
                 for (int q = 0; q < r->n; ++q) {

@@ -11,7 +11,8 @@ overwrites it with the match/mismatch matrix (pyabpoa.pyx:114-120 with abpoa_ali
 custom matrices; this front end honours the file.
 
 Additive: `msa_aligner.msa_batch(list_of_read_sets, ...)` aligns many independent read-sets in one call -- the shape the
-GPU wants (one read-set per wavefront, every set advancing one read per round)."""
+GPU wants (one read-set per wavefront, every set advancing one read per round); with out_gfa=True the results carry the graph
+in the order of the reference's GFA output (`.gfa`)."""
 import os
 
 from . import api
@@ -21,6 +22,7 @@ class msa_result:
     def __init__(self, n_seq, n_cons, clu_n_seq, clu_read_ids, cons_len, cons_seq, cons_cov, msa_len, msa_seq):
         self.n_seq, self.n_cons, self.clu_n_seq, self.clu_read_ids = n_seq, n_cons, clu_n_seq, clu_read_ids
         self.cons_len, self.cons_seq, self.cons_cov, self.msa_len, self.msa_seq = cons_len, cons_seq, cons_cov, msa_len, msa_seq
+        self.gfa = None      # (additive: msa_batch(..., out_gfa=True))
 
     def print_msa(self):
         if not self.msa_seq:
@@ -92,9 +94,13 @@ class msa_aligner:
         r = api.msa_batch([list(seqs)], self.params, out_cons=bool(out_cons), out_msa=bool(out_msa), lib=self._lib)[0]
         return self._wrap(seqs, r, out_cons, out_msa)
 
-    def msa_batch(self, read_sets, out_cons=True, out_msa=False, n_threads=0, progressive=False):
+    def msa_batch(self, read_sets, out_cons=True, out_msa=False, n_threads=0, progressive=False, out_gfa=False):
         """Many independent read-sets (lists of sequences) in one engine call -> list of msa_result.
-        progressive: the reads of every set in guide-tree order (abpoa -p; msa() keeps the reference binding's signature, which forces it off)."""
+        progressive: the reads of every set in guide-tree order (abpoa -p; msa() keeps the reference binding's signature, which forces it off);
+        out_gfa: every result also carries `.gfa`, the graph as the reference's GFA output walks it (api.GfaView; api.format_gfa prints it)."""
         rs = api.msa_batch([list(s) for s in read_sets], self.params, out_cons=bool(out_cons), out_msa=bool(out_msa), n_threads=n_threads, lib=self._lib,
-                           progressive=bool(progressive))
-        return [self._wrap(s, r, out_cons, out_msa) for s, r in zip(read_sets, rs)]
+                           progressive=bool(progressive), out_gfa=bool(out_gfa))
+        res = [self._wrap(s, r, out_cons, out_msa) for s, r in zip(read_sets, rs)]
+        for w, r in zip(res, rs):
+            w.gfa = r.gfa if out_gfa else None
+        return res

@@ -17,6 +17,7 @@
  *
  *  (3) READ-SET BATCH API (abpoa_hip_msa_batch)         -- additive, no reference counterpart:
  *      progressive POA of many independent read-sets in lock-step rounds (SURVEY.md 8b "new entry").
+ *      Outputs: consensus, row-column MSA, and the graph as GFA (ABPOA_HIP_OUT_GFA, abpoa_hip_format_gfa).
  *
  * Error behaviour: the reference has no error returns on this path (fatal -> exit(1),
  * src/utils.c:91-116).  The flat API returns 0 on success and a negative ABPOA_HIP_E* code
@@ -28,6 +29,7 @@
 
 #include <stdint.h>
 #include <stddef.h>
+#include <stdio.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -182,6 +184,19 @@ typedef struct abpoa_hip_readset_t {
                                      qv weights, abpoa_msa1 src/abpoa_align.c:462-467 (quality - 32 with -Q)  */
 } abpoa_hip_readset_t;
 
+/* The graph of one read-set in the order the reference prints it as GFA (abpoa_generate_gfa, src/abpoa_output.c:168-268): a Kahn walk with a FIFO
+ * queue from the source; "printed id" = node id - 1.  Everything abpoa_hip_format_gfa needs but the names.  An empty graph leaves n_seg = 0. */
+typedef struct abpoa_hip_gfa_t {
+    int32_t  n_seg, n_link, n_path;   /* inner nodes; edges between inner nodes (the header's NL); reads of the set                     */
+    int32_t *seg_node;            /* [n_seg] printed ids in walk order                                                               */
+    uint8_t *seg_base;            /* [n_seg] residue codes                                                                           */
+    int32_t *link_off;            /* [n_seg+1] segment i owns link_from[link_off[i] .. link_off[i+1])                                */
+    int32_t *link_from;           /* [n_link] printed ids of the segment's predecessors in in_id order, the source left out          */
+    int64_t *path_off;            /* [n_path+1] read r (input order) owns path_node[path_off[r] .. path_off[r+1])                    */
+    int32_t *path_node;           /* printed ids of the nodes the read went through, in walk order (the formatter reverses a path
+                                     whose read went in as its reverse complement: abpoa_hip_msa_t.is_rc)                            */
+} abpoa_hip_gfa_t;
+
 typedef struct abpoa_hip_msa_t {
     int32_t  status;              /* ABPOA_HIP_OK or the first failing alignment's code              */
     int32_t  n_reads;
@@ -195,12 +210,18 @@ typedef struct abpoa_hip_msa_t {
     int64_t  n_cells;             /* DP cells over all alignments of the set                          */
     uint8_t *is_rc;               /* NULL unless ABPOA_HIP_AMB_STRAND: [n_reads] 1 where the reverse complement of the read
                                      went into the graph (abpoa_seq_t.is_rc, src/abpoa_align.c:331)   */
+    abpoa_hip_gfa_t *gfa;         /* NULL unless ABPOA_HIP_OUT_GFA: the graph as the reference's GFA output walks it   */
 } abpoa_hip_msa_t;
 
 #define ABPOA_HIP_OUT_CONS 0x1u   /* abpoa_para_t.out_cons */
 #define ABPOA_HIP_OUT_MSA  0x2u   /* abpoa_para_t.out_msa  */
 #define ABPOA_HIP_AMB_STRAND 0x4u /* abpoa_para_t.amb_strand (-s): a read whose best score is below min(qlen, nodes - 2) * max_mat / 3 is aligned
                                      again as its reverse complement and the better strand goes into the graph (src/abpoa_align.c:315-336) */
+
+/* The graph as GFA (the reference's -r 3; with ABPOA_HIP_OUT_CONS its -r 4): fills abpoa_hip_msa_t.gfa.  Keeps the read ids per edge as ABPOA_HIP_OUT_MSA
+ * does (abpoa_post_set_para, src/abpoa_align.c:145); the consensus is computed only with ABPOA_HIP_OUT_CONS -- its path is cons_node_id.  May be combined
+ * with ABPOA_HIP_OUT_MSA: both are filled. */
+#define ABPOA_HIP_OUT_GFA 0x10u
 
 /* abpoa_para_t.progressive_poa (-p): the reads of every set are aligned in the order of the reference's guide tree (src/abpoa_seed.c:231-324) -- the most
  * similar pair first, then always the read most similar to those already in the graph, similarity = Jaccard index of the reads' minimizer sketches.
@@ -239,6 +260,10 @@ int  abpoa_hip_msa_batch(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_
                          abpoa_hip_msa_t *out, unsigned flags, int n_threads);
 void abpoa_hip_free_msa(abpoa_hip_msa_t *r);
 void abpoa_hip_free_msa_array(abpoa_hip_msa_t *r, int n);   /* abpoa_hip_free_msa on r[0..n): one call for a whole batch (bindings whose calls are dear) */
+/* The text the reference prints for r->gfa (abpoa_generate_gfa): header, S / L lines in walk order, one P line per read -- names[i], or i + 1 where names
+ * or names[i] is NULL or empty; reversed with '-' where r->is_rc[i] -- and with out_cons the consensus path from r->cons_node_id.  m: alphabet size (5: nucleotide
+ * letters, else amino acids).  Nothing is written for a record without gfa or with n_seg = 0.  Returns 0, or ABPOA_HIP_EINVAL.  Usable without a GPU. */
+int  abpoa_hip_format_gfa(const abpoa_hip_msa_t *r, int m, const char *const *names, int out_cons, FILE *fp);
 
 /* Phase timers of the last abpoa_hip_msa_batch call (seconds): host graph work, engine calls. */
 typedef struct abpoa_hip_msa_timing_t {
@@ -249,6 +274,10 @@ typedef struct abpoa_hip_msa_timing_t {
                                      With ABPOA_HIP_STRICT=1 in the environment such a call fails with ABPOA_HIP_ESTRICT instead of slowing down silently. */
 } abpoa_hip_msa_timing_t;
 void abpoa_hip_get_msa_timing(abpoa_hip_msa_timing_t *out);
+/* GFA output of the last abpoa_hip_msa_batch call, device-resident driver: durations of its two kernels (hipEvents, summed over the passes) and the bytes of
+ * its result download.  All zero for a call without ABPOA_HIP_OUT_GFA. */
+typedef struct abpoa_hip_gfa_timing_t { double walk_ms, fill_ms; int64_t d2h_bytes; } abpoa_hip_gfa_timing_t;
+void abpoa_hip_get_gfa_timing(abpoa_hip_gfa_timing_t *out);
 /* Why the n_host_sets read-sets of the last abpoa_hip_msa_batch call left the device-resident driver: out12[r] = sets with reason r -- 1 node slots at the
  * first read, 2 predecessor-list slots, 3 cigar slots, 4 node slots while a read was fused, 5 edge / aligned slots of one node, 6 projected graph growth,
  * 7 row-order walk, 8 MSA rank walk, 9 DP arena too small for the bands, 10 other DP status, 0 other, 11 the job's options (or a pass that did not fit the
