@@ -342,23 +342,6 @@ int abpoa_hip__last_aln(const uint8_t *seq0, int len0, int *out8, int reset) {
     if (reset) g_last_aln.clear();
     return found;
 }
-}
-namespace abpoa_hip {
-abpoa_hip_gfa_t *gfa_alloc(int n_seg, int n_link, int n_path, int64_t n_path_node) {
-    abpoa_hip_gfa_t *g = (abpoa_hip_gfa_t *)calloc(1, sizeof(*g));
-    if (!g) return nullptr;
-    g->n_seg = n_seg; g->n_link = n_link; g->n_path = n_path;
-    g->seg_node = (int32_t *)calloc((size_t)n_seg + 1, 4); g->seg_base = (uint8_t *)calloc((size_t)n_seg + 1, 1); g->link_off = (int32_t *)calloc((size_t)n_seg + 1, 4);
-    g->link_from = (int32_t *)calloc((size_t)n_link + 1, 4); g->path_off = (int64_t *)calloc((size_t)n_path + 1, 8); g->path_node = (int32_t *)calloc((size_t)n_path_node + 1, 4);
-    if (!g->seg_node || !g->seg_base || !g->link_off || !g->link_from || !g->path_off || !g->path_node) { gfa_free(g); return nullptr; }
-    return g;
-}
-void gfa_free(abpoa_hip_gfa_t *g) {
-    if (!g) return;
-    free(g->seg_node); free(g->seg_base); free(g->link_off); free(g->link_from); free(g->path_off); free(g->path_node); free(g);
-}
-}
-extern "C" {
 // reference abpoa_generate_gfa, src/abpoa_output.c:182-264 (letters: ab_char256_table, src/abpoa_seq.c)
 int abpoa_hip_format_gfa(const abpoa_hip_msa_t *r, int m, const char *const *names, int out_cons, FILE *fp) {
     if (!r || !fp) return ABPOA_HIP_EINVAL;

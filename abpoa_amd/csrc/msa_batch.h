@@ -13,9 +13,6 @@ void cigar_digest_set(const uint8_t *seq0, int len0, uint64_t value);      // (t
 // ... and, under the same switch, the device-resident driver notes the result record of each set's LAST alignment (abpoa_hip__last_aln): n_matched_bases, n_aln_bases,
 // node_s, node_e, query_s, query_e, n_cigar, status -- the only place where the matched-base count of the direction-plane backtrack shows
 void last_aln_set(const uint8_t *seq0, int len0, const int32_t *v8);
-// A zeroed abpoa_hip_gfa_t with room for the given counts (libc malloc; NULL when memory is short); gfa_free releases it (NULL is fine)
-abpoa_hip_gfa_t *gfa_alloc(int n_seg, int n_link, int n_path, int64_t n_path_node);
-void gfa_free(abpoa_hip_gfa_t *g);
 int run_msa_batch(const abpoa_hip_scoring_t *sc, int n_sets, const abpoa_hip_readset_t *sets, abpoa_hip_msa_t *out,
                   unsigned flags, int n_threads, int n_groups, AlignerFactory make, abpoa_hip_msa_timing_t *timing);
 }

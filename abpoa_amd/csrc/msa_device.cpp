@@ -21,6 +21,7 @@
 #include "dir_plane.h"
 #include "msa_batch.h"
 #include "msa_device_debug.h"
+#include "msa_device_layout.h"
 #include "msa_device_plan.h"
 #include "routing.h"
 
@@ -87,31 +88,17 @@ struct Cache { Arena in, graph, rows, planes, out, msa, gfa; hipStream_t stream 
                 *a = Arena(); } } };
 Cache g_cache[MSA_DEVICE_SLOTS]; std::mutex g_cache_mu[MSA_DEVICE_SLOTS];      // one per worker of the multi-device batch call
 
-struct Layout {                // byte offsets inside the three device blobs
-    // in blob (uploaded): sets, read tables, reads, score matrix
-    // (o_rc, o_wrc: device only, behind the uploaded part)
-    size_t o_sets, o_roff, o_rlen, o_reads, o_mat, o_rargs, o_msaoff_h, o_gfaoff_h, o_wts, in_bytes, o_rc, o_wrc, in_dev_bytes;
-    // graph blob (device only, the tail of it downloaded at the end): per-node pools
-    size_t o_cnode, o_ccov, o_cbase, o_isrc, o_gcnt;
-    size_t o_gwalk, o_gorw, o_goff;      // GFA output (GfaDev): walk order, ORed read bitsets, the host's offsets -- zero bytes unless the job asked for it
-    size_t o_state, o_base, o_nin, o_nout, o_naln, o_in, o_out, o_outw, o_inx, o_outx, o_outwx, o_aln, o_nread, o_row, o_order0, o_order1, o_rid, o_mrank,
-            o_msaoff, o_tout, o_toutw, o_tin, graph_bytes;
-    // rows blob: DP inputs / outputs per row, descriptors, cigars, scratch
-    size_t o_ticket, o_aln_desc, o_out_rec, o_rbase, o_rsd, o_rpd, o_rnid, o_rrem, o_poff, o_pred, o_bsn, o_esn, o_coff, o_rmi, o_cigar, o_scratch, o_ooff,
-            o_orow, o_left, o_right, o_act, o_outfwd, o_cigfwd, o_retry, rows_bytes;
-};
-
 // What the stages of one job share (run_msa_device_body runs them in order)
 struct Job {
     DevicePlan pl; const abpoa_hip_readset_t *sets; int n_sets, n_threads, device, slot;
-    Cache *C; Layout L; size_t dl_bytes;      // dl_bytes: the downloaded head of the graph blob
+    Cache *C; Layout L; EventSlots ev;
     bool any_w, rest_up; int64_t split_at;      // per-base weights given; the reads of the later rounds are on their way; where they start in the read pool
     PoaDev p; DevBatch b, b_rc, b_r;      // kernel arguments of the graph kernels and of the row loops (b_rc: the -s retry, b_r: the all-rounds kernel)
     bool dbg_sync, use_rounds; size_t rounds_lds;
-    std::vector<int64_t> msa_off;
-    GfaDev g; std::vector<int64_t> gfa_off;      // GFA output: kernel arguments; per set first segment, first link, first path entry, path capacity
-    size_t go_seg, go_loff, go_lfrom, go_poff, go_pnode, go_base, go_cnt, go_bytes; int64_t gfa_d2h;      // byte offsets of the result pools in Cache.gfa
+    MsaLayout M;
+    GfaDev g; GfaLayout G;      // GFA output: kernel arguments; where each set's record lies in the result pools of Cache.gfa
     double t_begin, t_queue, t_done;
+    const PoaState *host_state() const { return (const PoaState *)(C->graph.host + L.o_state); }      // (downloaded by queue_job)
 };
 
 }  // namespace
@@ -155,50 +142,7 @@ int acquire_cache_slot(Cache &C, int device) {
     return 0;
 }
 
-// ---- stage 2: byte offsets of every pool inside the three device blobs
-void lay_out(const DevicePlan &pl, int n_sets, bool any_w, Layout &L, size_t *dl_bytes) {
-    const abpoa_hip_scoring_t *sc = &pl.sc; const bool gen_io = pl.gen_io();
-    size_t o = 0;
-    auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes); return at; };
-    // (o_rargs, o_msaoff_h: host-side staging only)
-    L.o_sets = take(sizeof(PoaSet) * n_sets); L.o_roff = take(8 * (pl.tot_reads + 1)); L.o_rlen = take(4 * (pl.tot_reads + 1)); L.o_mat = take(4 * sc->m * sc->m);
-    L.o_rargs = take(poa_rounds_args_bytes()); L.o_msaoff_h = take(pl.want_msa ? 8 * (size_t)n_sets : 0);
-    L.o_gfaoff_h = take(pl.want_gfa ? 32 * (size_t)n_sets : 0);
-    L.o_wts = take(any_w ? 4 * (size_t)(pl.tot_bases + 64) : 0);      // (per-base weights, -Q: in front of the reads, so that they go up with the first part)
-    L.o_reads = take(pl.tot_bases + 64); L.in_bytes = o;      // reads last: they go up in two parts
-    // -s: reverse complements / reversed weights of the reads under retry
-    L.o_rc = take(pl.amb ? pl.tot_bases + 64 : 0); L.o_wrc = take(pl.amb && any_w ? 4 * (size_t)(pl.tot_bases + 64) : 0); L.in_dev_bytes = o;
-    o = 0;
-    L.o_state = take(sizeof(PoaState) * n_sets);
-    // downloaded part first, contiguous: per-set state and the consensus results
-    L.o_cnode = take(4 * pl.cons_tot); L.o_ccov = take(4 * pl.cons_tot); L.o_cbase = take(pl.cons_tot); L.o_isrc = take(pl.amb ? (size_t)pl.tot_reads : 0);
-    L.o_gcnt = take(pl.want_gfa ? 12 * (size_t)n_sets : 0);
-    *dl_bytes = o;
-    L.o_order0 = take(4 * pl.node_tot); L.o_order1 = take(4 * pl.node_tot); L.o_base = take(pl.node_tot); L.o_nout = take(pl.node_tot);
-    L.o_out = take(4 * pl.node_tot * POA_HOT); L.o_outw = take(4 * pl.node_tot * POA_HOT); L.o_nread = take(4 * pl.node_tot);
-    L.o_outx = take(4 * pl.node_tot * (size_t)(pl.out_cap - POA_HOT)); L.o_outwx = take(4 * pl.node_tot * (size_t)(pl.out_cap - POA_HOT));
-    L.o_inx = take(4 * pl.node_tot * (size_t)(pl.in_cap - POA_HOT));
-    L.o_nin = take(pl.node_tot); L.o_naln = take(pl.node_tot); L.o_in = take(4 * pl.node_tot * POA_HOT); L.o_aln = take(4 * pl.node_tot * (size_t)pl.aln_cap);
-    L.o_row = take(4 * pl.node_tot);
-    L.o_rid = take(8 * pl.node_tot * (size_t)pl.out_cap * (size_t)pl.rid_words); L.o_mrank = take(pl.want_msa ? 4 * pl.node_tot : 0);
-    L.o_msaoff = take(pl.want_msa ? 8 * (size_t)n_sets : 0);
-    L.o_gwalk = take(pl.want_gfa ? 4 * pl.node_tot : 0); L.o_gorw = take(pl.want_gfa ? 8 * pl.node_tot * (size_t)pl.rid_words : 0); L.o_goff = take(pl.want_gfa ? 32 * (size_t)n_sets : 0);
-    L.o_tout = take(4 * pl.term_tot); L.o_toutw = take(4 * pl.term_tot); L.o_tin = take(4 * pl.term_tot);
-    L.graph_bytes = o;
-    o = 0;
-    L.o_ticket = take(4 * POA_CU_TICKETS);
-    L.o_aln_desc = take(sizeof(AlnDesc) * n_sets); L.o_out_rec = take(sizeof(AlnOut) * n_sets);
-    L.o_rbase = take(pl.node_tot); L.o_rsd = take(pl.node_tot); L.o_rpd = take(8 * pl.node_tot); L.o_rnid = take(4 * pl.node_tot); L.o_rrem = take(4 * pl.node_tot);
-    L.o_poff = take(4 * pl.node_tot); L.o_pred = take(4 * (pl.pred_tot + 1));
-    L.o_bsn = take(4 * pl.node_tot); L.o_esn = take(4 * pl.node_tot); L.o_coff = take(8 * pl.node_tot); L.o_rmi = take(4 * pl.node_tot);
-    L.o_cigar = take(8 * pl.cig_tot); L.o_scratch = take(4 * pl.scr_tot);
-    // general kernel (rows_general.h): successor CSR, band state per row, the "row is part of the alignment" bytes (all ones: no sub-graph alignments here)
-    L.o_ooff = take(gen_io ? 4 * pl.node_tot : 0); L.o_orow = take(gen_io ? 4 * (pl.pred_tot + 1) : 0); L.o_left = take(gen_io ? 4 * pl.node_tot : 0);
-    L.o_right = take(gen_io ? 4 * pl.node_tot : 0); L.o_act = take(gen_io ? pl.node_tot : 0);
-    L.o_outfwd = take(pl.amb ? sizeof(AlnOut) * n_sets : 0); L.o_cigfwd = take(pl.amb ? 8 * pl.cig_tot : 0); L.o_retry = take(pl.amb ? (size_t)n_sets : 0);
-    L.rows_bytes = o;
-}
-
+// ---- stage 2, byte offsets of every pool inside the three device blobs: lay_out_device (msa_device_layout.h)
 // ---- stage 3: the whole job must fit (the caller splits very large jobs): checked on the computed layout, before any cached buffer is given up; then the
 //      pools grow to it
 int fit_device(Job &J) {
@@ -226,10 +170,9 @@ int fit_device(Job &J) {
     }
     int rc;
     if ((rc = C.in.need_dev(L.in_dev_bytes)) || (rc = C.in.need_host(L.in_bytes)) || (rc = C.graph.need_dev(L.graph_bytes)) || (rc =
-            C.graph.need_host(J.dl_bytes)) ||
+            C.graph.need_host(L.dl_bytes)) ||
         (rc = C.rows.need_dev(L.rows_bytes)) || (rc = C.planes.need_dev((size_t)pl.plane_tot))) return rc;
-    const int n_ev = 4 * pl.max_reads + 8;
-    while ((int)C.ev.size() < n_ev) { hipEvent_t e; HIP_OK(hipEventCreate(&e), ABPOA_HIP_ENODEV); C.ev.push_back(e); }
+    while ((int)C.ev.size() < J.ev.count()) { hipEvent_t e; HIP_OK(hipEventCreate(&e), ABPOA_HIP_ENODEV); C.ev.push_back(e); }
     return 0;
 }
 
@@ -249,17 +192,7 @@ int upload_reads(Job &J) {
     // Reads are laid out round by round (read k of every set, then read k + 1 ...): the first two rounds go up at once, the rest is staged
     // and copied while the GPU already works on round 1 (config 2: 50 MB of residue codes, ~1 ms of staging + ~1 ms of PCIe)
     int64_t *roff = (int64_t *)(hi + L.o_roff); int32_t *rlen = (int32_t *)(hi + L.o_rlen); uint8_t *rd = hi + L.o_reads;
-    J.split_at = 0;
-    {
-        int64_t at = 0;
-        for (int k = 0; k < pl.max_reads; ++k) {
-            if (k == 2) J.split_at = at;
-            for (int s = 0; s < J.n_sets; ++s) if (k < J.sets[s].n_reads) { const int64_t ri = pl.ps[s].read0 + k; roff[ri] = at; rlen[ri] = J.sets[s].lens[k];
-                    at += J.sets[s].lens[k]; }
-        }
-        if (pl.max_reads <= 2) J.split_at = at;
-        roff[pl.tot_reads] = at;
-    }
+    J.split_at = fill_read_tables(pl, J.n_sets, J.sets, roff, rlen);
     stage_reads(J, 0, 2);
     if (J.any_w) {      // weights of every read, same offsets as the bases; a read (or a set) without weights counts 1 per base
         int32_t *wd = (int32_t *)(hi + L.o_wts);
@@ -279,92 +212,16 @@ int upload_reads(Job &J) {
     return 0;
 }
 
-// ---- stage 5: arguments of the graph kernels
-void fill_poa_dev(Job &J) {
-    const DevicePlan &pl = J.pl; Cache &C = *J.C; const Layout &L = J.L; const abpoa_hip_scoring_t *sc = &pl.sc; PoaDev &p = J.p; const bool gen_io = pl.gen_io();
-    uint8_t *di = C.in.dev, *dg = C.graph.dev, *dr = C.rows.dev;
-    memset(&p, 0, sizeof(p));
-    p.n_sets = J.n_sets; p.m = sc->m; p.max_mat = sc->max_mat; p.min_mis = sc->min_mis; p.o1 = sc->gap_open1; p.e1 = sc->gap_ext1; p.o2 = sc->gap_open2;
-    p.e2 = sc->gap_ext2;
-    p.wb = sc->wb; p.wf = sc->wf; p.gap_mode = sc->gap_mode; p.max_qlen = pl.max_qlen;
-    p.last_pass = pl.node_factor >= 6.0 ? 1 : 0;      // (msa_passes.cpp run_pass_ladder: 3x, 4.5x, 6x, 4096x; the 6x pass and the last)
-    p.in_cap = pl.in_cap; p.out_cap = pl.out_cap;
-    p.dig_on = cigar_digest_on() ? 1 : 0;      // (tests: the fuse phase folds every graph cigar into PoaState.cigar_dig)
-    // (the reference's own row order where the best cell is the FIRST row that reaches the maximum: local and extension mode, ref :1012-1026; the remaining
-    //  length where something reads it: the adaptive band and the z-drop test)
-    p.aln_cap = pl.aln_cap; p.rid_words = pl.rid_words; p.order_mode = (pl.local || pl.extend) ? 1 : 0; p.banded = (sc->wb >= 0 || sc->zdrop > 0) ? 1 : 0;
-    p.general = pl.general ? 1 : 0; p.msa_rows = 0; p.msa_cons = (pl.want_msa && pl.want_cons) ? 1 : 0;
-    // LDS tables of the order / rank kernels (two ints per node; the rank pass packs four tables into the same space): up to 6000 nodes = 52 KB, three
-    //  workgroups per CU
-    p.order_lds = (p.order_mode || pl.want_msa) ? std::min(((pl.max_node_cap + 3) & ~3), 6000) : 0;
-    // (the all-in-LDS order walk: what is left of 40 KB -- four workgroups per CU -- after 13 bytes a node goes to aligned-list entries, 2 bytes each)
-    p.order_ecap = p.order_mode ? std::max(1024, std::min(65535, (40 * 1024 - 128 - 13 * p.order_lds) / 2)) : 0;
-    if (!opt_int("ABPOA_HIP_ORDER_LDS", 1)) p.order_ecap = 0;      // (ABPOA_HIP_ORDER_LDS=0: the general walk everywhere)
-    // (tests: graphs above this many nodes take the walks with tables in memory)
-    { const int cap_ = opt_int("ABPOA_HIP_ORDER_CAP", -1); if (cap_ >= 0) p.order_lds = std::min(p.order_lds, cap_ & ~3); }
-    // per-row records of the prepare kernel in LDS (5 bytes a row, 40 KB at most: four workgroups per CU still fit)
-    p.lds_rows = pl.max_node_cap <= 8000 ? ((pl.max_node_cap + 3) & ~3) : 0;
-    p.sets = (const PoaSet *)(di + L.o_sets); p.state = (PoaState *)(dg + L.o_state);
-    p.read_off = (const int64_t *)(di + L.o_roff); p.read_len = (const int32_t *)(di + L.o_rlen); p.reads = di + L.o_reads;
-    p.wts = J.any_w ? (const int32_t *)(di + L.o_wts) : nullptr;
-    p.nd_base = dg + L.o_base; p.nd_nin = dg + L.o_nin; p.nd_nout = dg + L.o_nout; p.nd_naln = dg + L.o_naln;
-    p.nd_in = (int32_t *)(dg + L.o_in); p.nd_out = (int32_t *)(dg + L.o_out); p.nd_outw = (int32_t *)(dg + L.o_outw); p.nd_aln = (int32_t *)(dg + L.o_aln);
-    p.nd_inx = (int32_t *)(dg + L.o_inx); p.nd_outx = (int32_t *)(dg + L.o_outx); p.nd_outwx = (int32_t *)(dg + L.o_outwx);
-    p.nd_nread = (int32_t *)(dg + L.o_nread); p.nd_row = (int32_t *)(dg + L.o_row);
-    p.t_out = (int32_t *)(dg + L.o_tout); p.t_outw = (int32_t *)(dg + L.o_toutw); p.t_in = (int32_t *)(dg + L.o_tin);
-    p.nd_rid = (uint64_t *)(dg + L.o_rid); p.msa_rank = (int32_t *)(dg + L.o_mrank); p.msa_off = (const int64_t *)(dg + L.o_msaoff); p.msa_out = nullptr;
-    p.row_node[0] = (int32_t *)(dg + L.o_order0); p.row_node[1] = (int32_t *)(dg + L.o_order1);
-    p.scratch = (int32_t *)(dr + L.o_scratch);
-    p.aln = (AlnDesc *)(dr + L.o_aln_desc); p.out = (AlnOut *)(dr + L.o_out_rec);
-    p.row_base = dr + L.o_rbase; p.row_sdist = dr + L.o_rsd; p.row_pd = (uint32_t *)(dr + L.o_rpd); p.row_node_id = (int32_t *)(dr + L.o_rnid);
-    p.row_remain = (int32_t *)(dr + L.o_rrem);
-    p.pred_off = (int32_t *)(dr + L.o_poff); p.pred_row = (int32_t *)(dr + L.o_pred); p.cigar = (uint64_t *)(dr + L.o_cigar);
-    p.out_off = gen_io ? (int32_t *)(dr + L.o_ooff) : nullptr; p.out_row = gen_io ? (int32_t *)(dr + L.o_orow) : nullptr;
-    if (pl.amb) {
-        p.reads_rc = di + L.o_rc; p.wts_rc = J.any_w ? (int32_t *)(di + L.o_wrc) : nullptr; p.is_rc = dg + L.o_isrc; p.retry = dr + L.o_retry;
-        p.out_fwd = (AlnOut *)(dr + L.o_outfwd); p.cigar_fwd = (uint64_t *)(dr + L.o_cigfwd);
-    }
-    p.cons_node = (int32_t *)(dg + L.o_cnode); p.cons_cov = (int32_t *)(dg + L.o_ccov); p.cons_base = dg + L.o_cbase;
-    // GFA output: the walk's counters and queue in LDS for graphs of up to 6000 nodes (48 KB), in memory above that and with ABPOA_HIP_ORDER_LDS=0
-    // (ABPOA_HIP_ORDER_CAP as for the order / rank walks); the result pools are laid out once the walk has counted (queue_job)
-    memset(&J.g, 0, sizeof(J.g));
-    if (pl.want_gfa) {
-        J.g.lds_cap = opt_int("ABPOA_HIP_ORDER_LDS", 1) ? std::min(((pl.max_node_cap + 3) & ~3), 6000) : 0;
-        { const int cap_ = opt_int("ABPOA_HIP_ORDER_CAP", -1); if (cap_ >= 0) J.g.lds_cap = std::min(J.g.lds_cap, cap_ & ~3); }
-        J.g.walk = (int32_t *)(dg + L.o_gwalk); J.g.cnt = (int32_t *)(dg + L.o_gcnt); J.g.orw = (uint64_t *)(dg + L.o_gorw); J.g.off = (const int64_t *)(dg + L.o_goff);
-    }
-}
-
+// ---- stage 5, arguments of the graph kernels: bind_poa_dev (msa_device_layout.h)
 // ---- stage 6: arguments of the row-loop kernels (b_rc: the -s retry in the general kernel)
 int fill_dev_batch(Job &J, bool *want_general) {
-    const DevicePlan &pl = J.pl; Cache &C = *J.C; const Layout &L = J.L; const abpoa_hip_scoring_t *sc = &pl.sc; const PoaDev &p = J.p; DevBatch &b = J.b, &b_rc = J.b_rc;
-    uint8_t *di = C.in.dev, *dr = C.rows.dev; const bool gen_io = pl.gen_io(); int rc;
+    const DevicePlan &pl = J.pl; Cache &C = *J.C; DevBatch &b = J.b; int rc;
     memset(&b, 0, sizeof(b));
-    b.n = J.n_sets; b.m = sc->m;
+    b.n = J.n_sets; b.m = pl.sc.m;
     if ((rc = final_lds_plan(pl, J.n_sets, J.sets, b))) { set_err("local alignment outside the device row loop's range"); return rc; }
     // caller falls back to the host driver
     if (!pl.local && !pl.general && !fast_loop_fits(b.lds, pl.max_qlen)) { *want_general = true; set_err("band too wide for the fast row loop"); return ABPOA_HIP_EINVAL; }
-    set_job_fields(b, *sc); b.ret_cigar = 1; b.rev_cigar = 0;
-    b.want_trace = 0; b.fresh_band = 1; b.want_lr = 0;
-    b.dbg = opt_int("ABPOA_HIP_DBG", 0);      // (diag.h)
-    b.mat = (const int32_t *)(di + L.o_mat); b.aln = p.aln; b.out = p.out;
-    b.dir_mode = pl.dir ? (pl.dir_wide ? 2 : 1) : 0; b.row_sdist = p.row_sdist; b.row_pd = p.row_pd;
-    b.query = p.reads; b.row_base = p.row_base; b.row_node_id = p.row_node_id; b.row_remain = p.row_remain; b.row_active = p.row_base;
-    b.pred_off = p.pred_off; b.pred_row = p.pred_row; b.out_off = p.pred_off; b.out_row = p.pred_row;
-    b.left = p.scratch; b.right = p.scratch;
-    if (gen_io) {
-        b.out_off = p.out_off; b.out_row = p.out_row; b.left = (int32_t *)(dr + L.o_left); b.right = (int32_t *)(dr + L.o_right); b.row_active = dr + L.o_act;
-    }
-    b.dp_beg_sn = (int32_t *)(dr + L.o_bsn); b.dp_end_sn = (int32_t *)(dr + L.o_esn); b.row_cell_off = (int64_t *)(dr + L.o_coff);
-    b.row_max_i = (int32_t *)(dr + L.o_rmi);
-    b.planes = C.planes.dev; b.cigar = p.cigar;
-    // -s: the forward run leaves max_pos_left/right behind (fast row loops: a post-pass, rows_fast.h; general kernel: its own arrays) and the retry starts
-    // from them -- the reference sorts, and so resets them, only before the forward alignment (src/abpoa_align.c:329 calls the DP directly)
-    b_rc = b;
-    if (pl.amb) {
-        b.want_lr = (sc->wb >= 0 && !pl.general) ? 1 : 0;
-        b_rc = b; b_rc.want_lr = 0; b_rc.fresh_band = sc->wb >= 0 ? 0 : 1;
-    }
+    bind_dev_batch(b, J.b_rc, pl, J.L, J.p, C.in.dev, C.rows.dev, C.planes.dev);
     return 0;
 }
 
@@ -416,6 +273,44 @@ void plan_rounds(Job &J) {
     }
 }
 
+// ---- the two output tails of stage 8, the same steps each: lay out on the host what the device counted (the state block is down), grow the pools, upload the
+//      offsets, fill on the device, download in one piece, synchronise
+// MSA rows: rows x columns bytes per set, back to back
+int queue_msa_output(Job &J, DeviceDebug &dbg) {
+    Cache &C = *J.C; const Layout &L = J.L; hipStream_t st = C.stream; uint8_t *hi = C.in.host; int rc;
+    J.M = lay_out_msa(J.pl, J.n_sets, J.sets, J.host_state());
+    if (J.M.total <= 0) return 0;
+    const size_t total = (size_t)J.M.total, off_bytes = 8 * (size_t)J.n_sets;
+    if ((rc = C.msa.need_dev(total)) || (rc = C.msa.need_host(total))) return rc;
+    memcpy(hi + L.o_msaoff_h, J.M.off.data(), off_bytes);
+    HIP_OK(hipMemcpyAsync(C.graph.dev + L.o_msaoff, hi + L.o_msaoff_h, off_bytes, hipMemcpyHostToDevice, st), ABPOA_HIP_ELAUNCH);
+    J.p.msa_out = C.msa.dev;
+    HIP_OK(launch_poa_msa_fill(J.p, st), ABPOA_HIP_ELAUNCH);
+    if (dbg.stage("msa fill", J.pl.max_reads)) return ABPOA_HIP_ELAUNCH;
+    HIP_OK(hipMemcpyAsync(C.msa.host, C.msa.dev, total, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);
+    HIP_OK(hipStreamSynchronize(st), ABPOA_HIP_ELAUNCH);
+    return 0;
+}
+// GFA output, phase 2: segment, link and path pools of the sets back to back (the walk's counts came down with the state block)
+int queue_gfa_output(Job &J, DeviceDebug &dbg) {
+    Cache &C = *J.C; const Layout &L = J.L; hipStream_t st = C.stream; uint8_t *hi = C.in.host, *hg = C.graph.host, *dg = C.graph.dev; int rc;
+    J.G = lay_out_gfa(J.pl, J.n_sets, J.sets, J.host_state(), (const int32_t *)(hg + L.o_gcnt));
+    if (!J.G.bytes) return 0;
+    const size_t off_bytes = 32 * (size_t)J.n_sets; hipEvent_t *eg = C.ev.data() + J.ev.gfa();
+    if ((rc = C.gfa.need_dev(J.G.bytes)) || (rc = C.gfa.need_host(J.G.bytes))) return rc;
+    memcpy(hi + L.o_gfaoff_h, J.G.off.data(), off_bytes);
+    HIP_OK(hipMemcpyAsync(dg + L.o_goff, hi + L.o_gfaoff_h, off_bytes, hipMemcpyHostToDevice, st), ABPOA_HIP_ELAUNCH);
+    bind_gfa_pools(J.g, J.G, C.gfa.dev);
+    HIP_OK(hipEventRecord(eg[2], st), ABPOA_HIP_ELAUNCH);
+    HIP_OK(launch_poa_gfa_fill(J.p, J.g, st), ABPOA_HIP_ELAUNCH);
+    HIP_OK(hipEventRecord(eg[3], st), ABPOA_HIP_ELAUNCH);
+    if (dbg.stage("gfa fill", J.pl.max_reads)) return ABPOA_HIP_ELAUNCH;
+    HIP_OK(hipMemcpyAsync(C.gfa.host, C.gfa.dev, J.G.o_cnt, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);
+    HIP_OK(hipMemcpyAsync(C.gfa.host + J.G.o_cnt, dg + L.o_gcnt, 12 * (size_t)J.n_sets, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);      // (the fill kernel's flags)
+    HIP_OK(hipStreamSynchronize(st), ABPOA_HIP_ELAUNCH);
+    return 0;
+}
+
 // ---- stage 8: the whole progressive alignment, queued back to back (ABPOA_HIP_DEVSYNC=1: synchronise and report after every kernel), the downloads
 int queue_job(Job &J, DeviceDebug &dbg) {
     const DevicePlan &pl = J.pl; Cache &C = *J.C; const Layout &L = J.L; PoaDev &p = J.p; const DevBatch &b = J.b;
@@ -426,12 +321,12 @@ int queue_job(Job &J, DeviceDebug &dbg) {
     if (pl.gen_io()) HIP_OK(hipMemsetAsync(dr + L.o_act, 1, (size_t)pl.node_tot, st), ABPOA_HIP_ELAUNCH);
     if (pl.amb) HIP_OK(hipMemsetAsync(dg + L.o_isrc, 0, (size_t)pl.tot_reads, st), ABPOA_HIP_ELAUNCH);
     J.t_queue = now_s();
-    HIP_OK(hipEventRecord(C.ev[0], st), ABPOA_HIP_ELAUNCH);
+    HIP_OK(hipEventRecord(C.ev[J.ev.job_begin()], st), ABPOA_HIP_ELAUNCH);
     if (stage("upload", 0)) return ABPOA_HIP_ELAUNCH;
     HIP_OK(launch_poa_init(p, st), ABPOA_HIP_ELAUNCH);
     if (stage("init", 0)) return ABPOA_HIP_ELAUNCH;
     dbg.graph_check(0);
-    HIP_OK(hipEventRecord(C.ev[1], st), ABPOA_HIP_ELAUNCH);
+    HIP_OK(hipEventRecord(C.ev[J.ev.after_init()], st), ABPOA_HIP_ELAUNCH);
     for (int k = 1; k < pl.max_reads; ++k) {
         if (k == 2 && !J.rest_up) {      // round 1 is queued: stage and send the reads of the later rounds behind it
             stage_reads(J, 2, pl.max_reads);
@@ -442,13 +337,13 @@ int queue_job(Job &J, DeviceDebug &dbg) {
             J.rest_up = true;
         }
         if (J.use_rounds && k == 2) {      // rounds 2 .. n - 1 of every set in one launch
-            HIP_OK(hipEventRecord(C.ev[2], st), ABPOA_HIP_ELAUNCH);
+            HIP_OK(hipEventRecord(C.ev[J.ev.rounds_begin()], st), ABPOA_HIP_ELAUNCH);
             HIP_OK(launch_poa_rounds(p, J.b_r, (int32_t *)(dr + L.o_ticket), C.in.host + L.o_rargs, J.slot, 2, J.rounds_lds, st), ABPOA_HIP_ELAUNCH);
-            HIP_OK(hipEventRecord(C.ev[3], st), ABPOA_HIP_ELAUNCH);
+            HIP_OK(hipEventRecord(C.ev[J.ev.rounds_end()], st), ABPOA_HIP_ELAUNCH);
             break;
         }
         p.round = k;
-        hipEvent_t *e = C.ev.data() + 4 * k;
+        hipEvent_t *e = C.ev.data() + J.ev.round(k);
         if (p.order_mode) { HIP_OK(launch_poa_order(p, st), ABPOA_HIP_ELAUNCH); if (stage("row order", k)) return ABPOA_HIP_ELAUNCH; dbg.order_check(k); }
         HIP_OK(launch_poa_prepare(p, st), ABPOA_HIP_ELAUNCH);
         if (stage("prepare", k)) return ABPOA_HIP_ELAUNCH;
@@ -473,89 +368,36 @@ int queue_job(Job &J, DeviceDebug &dbg) {
     // ---- consensus on the device, then one small download: per-set state + consensus (node ids, bases, coverage)
     if (pl.want_cons) { HIP_OK(launch_poa_consensus(p, st), ABPOA_HIP_ELAUNCH); if (stage("consensus", pl.max_reads)) return ABPOA_HIP_ELAUNCH; }
     if (pl.want_msa) { HIP_OK(launch_poa_msa_rank(p, st), ABPOA_HIP_ELAUNCH); if (stage("msa rank", pl.max_reads)) return ABPOA_HIP_ELAUNCH; }
-    hipEvent_t *eg = C.ev.data() + 4 * pl.max_reads + 4;      // (four events behind the rounds': fit_device makes 4 * max_reads + 8)
+    hipEvent_t *eg = C.ev.data() + J.ev.gfa();
     if (pl.want_gfa) {      // GFA output, phase 1: the walk order and the segment / link counts of every set (they come down with the state block)
         HIP_OK(hipEventRecord(eg[0], st), ABPOA_HIP_ELAUNCH);
         HIP_OK(launch_poa_gfa_walk(p, J.g, st), ABPOA_HIP_ELAUNCH);
         HIP_OK(hipEventRecord(eg[1], st), ABPOA_HIP_ELAUNCH);
         if (stage("gfa walk", pl.max_reads)) return ABPOA_HIP_ELAUNCH;
     }
-    HIP_OK(hipMemcpyAsync(hg, dg, J.dl_bytes, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);
+    HIP_OK(hipMemcpyAsync(hg, dg, L.dl_bytes, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);
     HIP_OK(hipStreamSynchronize(st), ABPOA_HIP_ELAUNCH);
-    // ---- MSA rows (reference abpoa_generate_rc_msa, src/abpoa_output.c:123-166): the rank pass left the column count of every set in its state; the results
-    //  are
-    //      laid out back to back (rows x columns bytes per set), filled on the device and downloaded in one piece
-    int64_t msa_total = 0;
-    if (pl.want_msa) {
-        const PoaState *hs_ = (const PoaState *)(hg + L.o_state);
-        J.msa_off.resize(J.n_sets);
-        for (int s = 0; s < J.n_sets; ++s) { J.msa_off[s] = msa_total; if (hs_[s].status == POA_ST_OK && hs_[s].n_nodes > 2) msa_total += (int64_t)(J.sets[s].n_reads
-                + (pl.want_cons ? 1 : 0)) * std::max(0, hs_[s].msa_len); }
-        if (msa_total > 0) {
-            if ((rc = C.msa.need_dev((size_t)msa_total)) || (rc = C.msa.need_host((size_t)msa_total))) return rc;
-            memcpy(hi + L.o_msaoff_h, J.msa_off.data(), 8 * (size_t)J.n_sets);
-            HIP_OK(hipMemcpyAsync(dg + L.o_msaoff, hi + L.o_msaoff_h, 8 * (size_t)J.n_sets, hipMemcpyHostToDevice, st), ABPOA_HIP_ELAUNCH);
-            p.msa_out = C.msa.dev;
-            HIP_OK(launch_poa_msa_fill(p, st), ABPOA_HIP_ELAUNCH);
-            if (stage("msa fill", pl.max_reads)) return ABPOA_HIP_ELAUNCH;
-            HIP_OK(hipMemcpyAsync(C.msa.host, C.msa.dev, (size_t)msa_total, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);
-            HIP_OK(hipStreamSynchronize(st), ABPOA_HIP_ELAUNCH);
-        }
-    }
-    // ---- GFA output, phase 2 (reference abpoa_generate_gfa, src/abpoa_output.c:168-268): segment, link and path pools of the sets back to back -- a path
-    //      has room for the bases of its set's reads, the kernel counts what it writes -- one upload of the offsets, the fill kernel, one download of the pools
-    J.go_bytes = 0; J.gfa_d2h = 0;
-    if (pl.want_gfa) {
-        const PoaState *hs_ = (const PoaState *)(hg + L.o_state); const int32_t *hc = (const int32_t *)(hg + L.o_gcnt);
-        J.gfa_off.assign(4 * (size_t)J.n_sets, 0);
-        int64_t seg_tot = 0, link_tot = 0, path_tot = 0;
-        for (int s = 0; s < J.n_sets; ++s) {
-            int64_t *o4 = J.gfa_off.data() + 4 * (size_t)s; o4[0] = seg_tot; o4[1] = link_tot; o4[2] = path_tot; o4[3] = 0;
-            if (hs_[s].status != POA_ST_OK || hs_[s].n_nodes <= 2 || hc[3 * s] <= 0) continue;
-            for (int r = 0; r < J.sets[s].n_reads; ++r) o4[3] += J.sets[s].lens[r];
-            seg_tot += hc[3 * s]; link_tot += hc[3 * s + 1]; path_tot += o4[3];
-        }
-        if (seg_tot > 0) {
-            size_t o = 0;
-            auto take = [&](size_t bytes) { size_t at = o; o = align_up(o + bytes); return at; };
-            J.go_seg = take(4 * (size_t)seg_tot); J.go_loff = take(4 * (size_t)(seg_tot + J.n_sets)); J.go_lfrom = take(4 * (size_t)link_tot);
-            J.go_poff = take(8 * (size_t)(pl.tot_reads + J.n_sets)); J.go_pnode = take(4 * (size_t)path_tot); J.go_base = take((size_t)seg_tot);
-            J.go_cnt = take(12 * (size_t)J.n_sets); J.go_bytes = o;
-            if ((rc = C.gfa.need_dev(J.go_bytes)) || (rc = C.gfa.need_host(J.go_bytes))) return rc;
-            memcpy(hi + L.o_gfaoff_h, J.gfa_off.data(), 32 * (size_t)J.n_sets);
-            HIP_OK(hipMemcpyAsync(dg + L.o_goff, hi + L.o_gfaoff_h, 32 * (size_t)J.n_sets, hipMemcpyHostToDevice, st), ABPOA_HIP_ELAUNCH);
-            uint8_t *dq = C.gfa.dev;
-            J.g.seg_node = (int32_t *)(dq + J.go_seg); J.g.link_off = (int32_t *)(dq + J.go_loff); J.g.link_from = (int32_t *)(dq + J.go_lfrom);
-            J.g.path_off = (int64_t *)(dq + J.go_poff); J.g.path_node = (int32_t *)(dq + J.go_pnode); J.g.seg_base = dq + J.go_base;
-            HIP_OK(hipEventRecord(eg[2], st), ABPOA_HIP_ELAUNCH);
-            HIP_OK(launch_poa_gfa_fill(p, J.g, st), ABPOA_HIP_ELAUNCH);
-            HIP_OK(hipEventRecord(eg[3], st), ABPOA_HIP_ELAUNCH);
-            if (stage("gfa fill", pl.max_reads)) return ABPOA_HIP_ELAUNCH;
-            HIP_OK(hipMemcpyAsync(C.gfa.host, dq, J.go_cnt, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);
-            HIP_OK(hipMemcpyAsync(C.gfa.host + J.go_cnt, dg + L.o_gcnt, 12 * (size_t)J.n_sets, hipMemcpyDeviceToHost, st), ABPOA_HIP_ELAUNCH);      // (the fill kernel's flags)
-            HIP_OK(hipStreamSynchronize(st), ABPOA_HIP_ELAUNCH);
-            J.gfa_d2h = (int64_t)J.go_bytes;
-        }
-    }
+    if (pl.want_msa && (rc = queue_msa_output(J, dbg))) return rc;
+    if (pl.want_gfa && (rc = queue_gfa_output(J, dbg))) return rc;
     J.t_done = now_s();
     return 0;
 }
 
 // ---- stage 9: kernel durations from the events; the all-rounds kernel's split by the ticks its sets spent per phase
 void fill_stats(const Job &J, DeviceRunStats *stats) {
-    const DevicePlan &pl = J.pl; Cache &C = *J.C; const Layout &L = J.L; const PoaDev &p = J.p;
+    const DevicePlan &pl = J.pl; Cache &C = *J.C; const PoaDev &p = J.p; const PoaState *hs_ = J.host_state();
     // (library built with -DABPOA_HIP_ORDER_PROF: the order walk's passes and ticks per kind, mean per set)
     if (opt_set("ABPOA_HIP_ORDER_PROF") && p.order_mode) {
-        const PoaState *hs_ = (const PoaState *)(C.graph.host + L.o_state); double a_[4] = {0, 0, 0, 0};
+        double a_[4] = {0, 0, 0, 0};
         for (int s = 0; s < J.n_sets; ++s) for (int i = 0; i < 4; ++i) a_[i] += (double)hs_[s].t_phase[i];
         fprintf(stderr, "[abpoa-hip] order walk per set: %.0f single-node passes x %.0f ticks, %.0f parallel passes x %.0f ticks\n", a_[2] / J.n_sets,
                 a_[2] > 0 ? a_[0] / a_[2] : 0.0, a_[3] / J.n_sets, a_[3] > 0 ? a_[1] / a_[3] : 0.0);
     }
     if (!stats) return;
     float ms = 0;
-    hipEvent_t prev = C.ev[1];
+    hipEvent_t prev = C.ev[J.ev.after_init()];
     for (int k = 1; k < (J.use_rounds ? 2 : pl.max_reads); ++k) {
-        hipEvent_t *e = C.ev.data() + 4 * k;
+        hipEvent_t *e = C.ev.data() + J.ev.round(k);
         (void)hipEventElapsedTime(&ms, prev, e[0]); stats->prepare_ms += ms;
         (void)hipEventElapsedTime(&ms, e[0], e[1]); stats->rows_ms += ms;
         (void)hipEventElapsedTime(&ms, e[1], e[2]); stats->tail_ms += ms;
@@ -563,8 +405,7 @@ void fill_stats(const Job &J, DeviceRunStats *stats) {
         prev = e[3];
     }
     if (J.use_rounds) {      // the all-rounds kernel: its duration, split by the shader-clock ticks the sets spent in each phase (PoaState.t_phase)
-        (void)hipEventElapsedTime(&ms, C.ev[2], C.ev[3]); stats->rounds_ms = ms; stats->rounds_launches = 1;
-        const PoaState *hs_ = (const PoaState *)(C.graph.host + L.o_state);
+        (void)hipEventElapsedTime(&ms, C.ev[J.ev.rounds_begin()], C.ev[J.ev.rounds_end()]); stats->rounds_ms = ms; stats->rounds_launches = 1;
         double tp[4] = {0, 0, 0, 0}, tmax = 0; for (int s = 0; s < J.n_sets; ++s) { double t_ = 0;
                 if (hs_[s].status == POA_ST_OK) stats->rounds_algo_bytes += hs_[s].algo_bytes - hs_[s].algo_bytes_before;
         for (int i = 0; i < 4; ++i) { tp[i] += (double)hs_[s].t_phase[i]; t_ += (double)hs_[s].t_phase[i]; } tmax = std::max(tmax, t_); }
@@ -588,70 +429,33 @@ void fill_stats(const Job &J, DeviceRunStats *stats) {
         }
     }
     if (pl.want_gfa) {
-        hipEvent_t *eg = C.ev.data() + 4 * pl.max_reads + 4;
+        hipEvent_t *eg = C.ev.data() + J.ev.gfa();
         (void)hipEventElapsedTime(&ms, eg[0], eg[1]); stats->gfa_walk_ms = ms;
-        if (J.go_bytes) { (void)hipEventElapsedTime(&ms, eg[2], eg[3]); stats->gfa_fill_ms = ms; }
-        stats->gfa_d2h_bytes = J.gfa_d2h;
+        if (J.G.bytes) { (void)hipEventElapsedTime(&ms, eg[2], eg[3]); stats->gfa_fill_ms = ms; }
+        stats->gfa_d2h_bytes = (int64_t)J.G.bytes;
     }
     stats->n_rounds = pl.max_reads > 0 ? pl.max_reads - 1 : 0; stats->device_s = J.t_done - J.t_queue;
 }
 
 // ---- stage 10: the results of the sets that finished; the others into `fallback`
 void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::vector<char> &need_fb, std::vector<SetFallback> *fallback) {
-    const DevicePlan &pl = J.pl; Cache &C = *J.C; const Layout &L = J.L; const PoaDev &p = J.p; const uint8_t *hg = C.graph.host;
-    const PoaState *hs = (const PoaState *)(hg + L.o_state);
-    const int32_t *h_cnode = (const int32_t *)(hg + L.o_cnode), *h_ccov = (const int32_t *)(hg + L.o_ccov); const uint8_t *h_cbase = hg + L.o_cbase;
+    const DevicePlan &pl = J.pl; Cache &C = *J.C; const PoaDev &p = J.p; const PoaState *hs = J.host_state();
     need_fb.assign(J.n_sets, 0);
     std::vector<AlnOut> h_out;      // (tests, with the cigar digests: the result record of every set's last alignment -- msa_batch.h last_aln_set)
     if (p.dig_on && J.n_sets > 0) { h_out.resize((size_t)J.n_sets);
             if (hipMemcpy(h_out.data(), p.out, sizeof(AlnOut) * (size_t)J.n_sets, hipMemcpyDeviceToHost) != hipSuccess) h_out.clear(); }
     parallel_ranges(std::min(J.n_threads, 8), J.n_sets, [&](int lo, int hi_) {
         for (int s = lo; s < hi_; ++s) {
-            abpoa_hip_msa_t &o_ = out[s];
-            memset(&o_, 0, sizeof(o_)); o_.n_reads = J.sets[s].n_reads;
-            // (only for a set that finished here: the record of a set that goes to another pass or to the host driver is overwritten there)
-            if (pl.amb && hs[s].status == POA_ST_OK) { o_.is_rc = (uint8_t *)calloc((size_t)std::max(1, J.sets[s].n_reads), 1);
-                    if (o_.is_rc) memcpy(o_.is_rc, hg + L.o_isrc + pl.ps[s].read0, (size_t)J.sets[s].n_reads); }
-            // (GFA output: the fill kernel's links or paths did not fit what the walk counted / the reads' bases: the set is redone like one whose walk failed)
-            const bool gfa_bad = pl.want_gfa && J.go_bytes && hs[s].status == POA_ST_OK && ((const int32_t *)(C.gfa.host + J.go_cnt))[3 * s + 2] != 0;
-            if (gfa_bad) { need_fb[s] = 1; free(o_.is_rc); o_.is_rc = nullptr; continue; }
-            if (hs[s].status != POA_ST_OK) { need_fb[s] = 1;
-                    if (J.dbg_sync) fprintf(stderr, "[poa-device] set %d falls back to the host driver: reason %d, %d nodes of %d\n", s, hs[s].reason,
-                    hs[s].n_nodes, pl.ps[s].node_cap); continue; }
-            o_.n_cells = hs[s].n_cells;
+            if (unpack_set(pl, J.L, J.M, J.G, J.sets[s], s, C.graph.host, C.msa.host, C.gfa.host, &out[s])) {
+                need_fb[s] = 1;
+                if (hs[s].status != POA_ST_OK && J.dbg_sync) fprintf(stderr, "[poa-device] set %d falls back to the host driver: reason %d, %d nodes of %d\n", s,
+                        hs[s].reason, hs[s].n_nodes, pl.ps[s].node_cap);
+                continue;
+            }
             if (p.dig_on && J.sets[s].n_reads > 0) cigar_digest_set(J.sets[s].seqs[0], J.sets[s].lens[0], hs[s].cigar_dig);
             if (!h_out.empty() && J.sets[s].n_reads > 1) { const AlnOut &a_ = h_out[(size_t)s];
                     const int32_t v8[8] = {a_.n_matched_bases, a_.n_aln_bases, a_.node_s, a_.node_e, a_.query_s, a_.query_e, a_.n_cigar, a_.status};
                     last_aln_set(J.sets[s].seqs[0], J.sets[s].lens[0], v8); }
-            if (pl.want_cons && hs[s].n_nodes > 2) {
-                const int len = hs[s].cons_len; const int64_t c0 = pl.ps[s].cons0;
-                o_.cons_len = len;
-                o_.cons_base = (uint8_t *)malloc(len + 1); o_.cons_cov = (int32_t *)malloc(4 * (len + 1)); o_.cons_node_id = (int32_t *)malloc(4 * (len + 1));
-                memcpy(o_.cons_base, h_cbase + c0, len); memcpy(o_.cons_cov, h_ccov + c0, 4 * (size_t)len);
-                memcpy(o_.cons_node_id, h_cnode + c0, 4 * (size_t)len);
-            }
-            if (pl.want_gfa) {      // (an empty graph: a record with n_seg = 0, as the host driver leaves it)
-                const int32_t *hc = (const int32_t *)(hg + L.o_gcnt); const uint8_t *hq = C.gfa.host;
-                const bool any = hs[s].n_nodes > 2 && J.go_bytes && hc[3 * s] > 0;
-                const int n_seg = any ? hc[3 * s] : 0, n_link = any ? hc[3 * s + 1] : 0, nr = J.sets[s].n_reads;
-                const int64_t *o4 = J.gfa_off.data() + 4 * (size_t)s;
-                const int64_t *poff = any ? (const int64_t *)(hq + J.go_poff) + pl.ps[s].read0 + s : nullptr;
-                const int64_t n_pn = any ? std::min<int64_t>(std::max<int64_t>(0, poff[nr]), o4[3]) : 0;
-                o_.gfa = gfa_alloc(n_seg, n_link, nr, n_pn);
-                if (o_.gfa && any) {
-                    memcpy(o_.gfa->seg_node, (const int32_t *)(hq + J.go_seg) + o4[0], 4 * (size_t)n_seg); memcpy(o_.gfa->seg_base, hq + J.go_base + o4[0], (size_t)n_seg);
-                    memcpy(o_.gfa->link_off, (const int32_t *)(hq + J.go_loff) + o4[0] + s, 4 * ((size_t)n_seg + 1));
-                    memcpy(o_.gfa->link_from, (const int32_t *)(hq + J.go_lfrom) + o4[1], 4 * (size_t)n_link);
-                    memcpy(o_.gfa->path_off, poff, 8 * ((size_t)nr + 1)); memcpy(o_.gfa->path_node, (const int32_t *)(hq + J.go_pnode) + o4[2], 4 * (size_t)n_pn);
-                }
-                if (!o_.gfa) o_.status = ABPOA_HIP_ENOMEM;
-            }
-            if (pl.want_msa && hs[s].n_nodes > 2) {      // (an empty graph has no MSA: the host driver leaves the record zeroed too)
-                const int len = std::max(0, hs[s].msa_len);
-                o_.msa_len = len; o_.msa_rows = J.sets[s].n_reads + (pl.want_cons ? 1 : 0);
-                o_.msa_base = (uint8_t *)malloc((size_t)o_.msa_rows * (len > 0 ? len : 1));
-                if (len > 0) memcpy(o_.msa_base, C.msa.host + J.msa_off[s], (size_t)o_.msa_rows * len);
-            }
         }
     });
     dbg.msa_check(hs, out);
@@ -664,7 +468,7 @@ void collect_results(const Job &J, DeviceDebug &dbg, abpoa_hip_msa_t *out, std::
 
 // ---- stage 11: ABPOA_HIP_VERBOSE: why sets left the pass
 void report_fallbacks(const Job &J, const std::vector<SetFallback> &fallback) {
-    const PoaState *hs = (const PoaState *)(J.C->graph.host + J.L.o_state);
+    const PoaState *hs = J.host_state();
     if (!opt_set("ABPOA_HIP_VERBOSE") || fallback.empty()) return;
     int n[MSA_HOST_REASONS] = {0};
     int dp_scores = 0;      // DP status: direction words could not decide (the arena too small for the rows' bands has a host reason of its own)
@@ -685,7 +489,7 @@ void report_fallbacks(const Job &J, const std::vector<SetFallback> &fallback) {
 }
 
 void finish_stats(const Job &J, const std::vector<char> &need_fb, DeviceRunStats *stats) {
-    const PoaState *hs = (const PoaState *)(J.C->graph.host + J.L.o_state);
+    const PoaState *hs = J.host_state();
     stats->cons_s = now_s() - J.t_done; stats->total_s = now_s() - J.t_begin;
     for (int s = 0; s < J.n_sets; ++s) if (!need_fb[s]) {
         stats->n_cells += hs[s].n_cells; stats->algo_bytes += hs[s].algo_bytes; stats->n_alignments += std::max(0, J.sets[s].n_reads - 1);
@@ -712,9 +516,9 @@ static int run_msa_device_body(const abpoa_hip_scoring_t *sc_in, int n_sets, con
     J.t_begin = now_s();
     J.pl = plan_device_job(sc_in, n_sets, sets, pass.node_factor, pass.flags, force_general);
     J.any_w = false; for (int s = 0; s < n_sets && !J.any_w; ++s) J.any_w = sets[s].weights != nullptr;
-    lay_out(J.pl, n_sets, J.any_w, J.L, &J.dl_bytes);
+    J.L = lay_out_device(J.pl, n_sets, J.any_w); J.ev = EventSlots{J.pl.max_reads};
     if ((rc = fit_device(J)) || (rc = upload_reads(J))) return rc;
-    fill_poa_dev(J);
+    bind_poa_dev(J.p, J.g, J.pl, J.L, n_sets, J.any_w, cigar_digest_on(), J.C->in.dev, J.C->graph.dev, J.C->rows.dev);
     if ((rc = fill_dev_batch(J, want_general))) return rc;
     plan_rounds(J);
     DeviceDebug dbg(&J.p, &J.pl.ps, sets, n_sets, J.pl.sc.m, J.pl.aln_cap, J.pl.max_reads, J.pl.want_msa, J.pl.amb, J.C->stream, J.pl.want_gfa);      // (ABPOA_HIP_DEVSYNC=1; msa_device_debug.h)

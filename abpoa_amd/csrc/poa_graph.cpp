@@ -2,6 +2,7 @@
 #include "poa_graph.h"
 #include <algorithm>
 #include <limits.h>
+#include <stdlib.h>
 #include <string.h>
 #include <stdexcept>
 
@@ -316,6 +317,20 @@ void PoaGraph::gfa(std::vector<int32_t> *seg_node, std::vector<uint8_t> *seg_bas
         for (size_t i = 0; i < seg_reads.size(); ++i) if (seg_reads[i][r >> 6] >> (r & 63) & 1) path_node->push_back((*seg_node)[i]);
         (*path_off)[(size_t)r + 1] = (int64_t)path_node->size();
     }
+}
+
+abpoa_hip_gfa_t *gfa_alloc(int n_seg, int n_link, int n_path, int64_t n_path_node) {
+    abpoa_hip_gfa_t *g = (abpoa_hip_gfa_t *)calloc(1, sizeof(*g));
+    if (!g) return nullptr;
+    g->n_seg = n_seg; g->n_link = n_link; g->n_path = n_path;
+    g->seg_node = (int32_t *)calloc((size_t)n_seg + 1, 4); g->seg_base = (uint8_t *)calloc((size_t)n_seg + 1, 1); g->link_off = (int32_t *)calloc((size_t)n_seg + 1, 4);
+    g->link_from = (int32_t *)calloc((size_t)n_link + 1, 4); g->path_off = (int64_t *)calloc((size_t)n_path + 1, 8); g->path_node = (int32_t *)calloc((size_t)n_path_node + 1, 4);
+    if (!g->seg_node || !g->seg_base || !g->link_off || !g->link_from || !g->path_off || !g->path_node) { gfa_free(g); return nullptr; }
+    return g;
+}
+void gfa_free(abpoa_hip_gfa_t *g) {
+    if (!g) return;
+    free(g->seg_node); free(g->seg_base); free(g->link_off); free(g->link_from); free(g->path_off); free(g->path_node); free(g);
 }
 
 }  // namespace abpoa_hip

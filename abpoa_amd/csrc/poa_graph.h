@@ -56,6 +56,10 @@ struct PoaNode {
     uint8_t base = 0;
 };
 
+// A zeroed abpoa_hip_gfa_t with room for the given counts (libc malloc; NULL when memory is short); gfa_free releases it (NULL is fine)
+abpoa_hip_gfa_t *gfa_alloc(int n_seg, int n_link, int n_path, int64_t n_path_node);
+void gfa_free(abpoa_hip_gfa_t *g);
+
 // Flattened snapshot handed to the engine; owns its arrays.
 struct FlatProblem {
     std::vector<uint8_t> row_base, row_active;
